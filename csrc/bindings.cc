@@ -13,6 +13,7 @@
 
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 
+#include <cstring>
 #include <thread>
 
 #include "backend.h"
@@ -204,7 +205,37 @@ void py_loopback_hierarchical(std::vector<at::Tensor> buckets,
     if (errs[r]) std::rethrow_exception(errs[r]);
 }
 
-DType dtype_arg(const at::Tensor& t) { return dtype_of(t); }
+// Copy a routed group's descs (followed by cum, if any) to the device.
+template <typename Desc>
+at::Tensor upload(const std::vector<Desc>& descs,
+                  const std::vector<int64_t>& cum, at::Device device) {
+  const size_t desc_bytes = sizeof(Desc) * descs.size();
+  const size_t cum_bytes = sizeof(int64_t) * cum.size();
+  std::vector<char> host(desc_bytes + cum_bytes);
+  std::memcpy(host.data(), descs.data(), desc_bytes);
+  std::memcpy(host.data() + desc_bytes, cum.data(), cum_bytes);
+  return at::from_blob(host.data(), {(int64_t)host.size()},
+                       at::TensorOptions().dtype(at::kByte))
+      .to(device);
+}
+
+// Route one slice's decode and launch every group on the current stream.
+void dequantize_slice(const at::Tensor& comp, at::Tensor& out, int64_t bits,
+                      int64_t bucket_size, bool skip_incomplete,
+                      int64_t src_stride, int nsrc, bool add) {
+  const DType dt = dtype_of(out);
+  auto stream =
+      c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(out.device().index());
+  const std::vector<DequantSlice> slices{
+      DequantSlice{comp.data_ptr<uint8_t>(), out.data_ptr(), out.numel(),
+                   (int)bits, (int)bucket_size, skip_incomplete}};
+  for (const DequantGroup& g :
+       route_dequantize(slices, dt, src_stride, nsrc, add)) {
+    auto dev = upload(g.descs, {}, out.device());
+    launch(g, static_cast<const DequantDesc*>(dev.data_ptr()), dt,
+           stream.stream());
+  }
+}
 
 // Compress a 1-D CUDA tensor; returns the uint8 compressed buffer
 // (zero-filled alignment padding so byte comparisons are well-defined).
@@ -224,82 +255,24 @@ at::Tensor py_quantize(at::Tensor x, int64_t bits, int64_t bucket_size,
                 "quantize: error feedback requires bucket_size % 8 == 0");
     fbp = feedback->data_ptr();
   }
-  const DType dt = dtype_arg(x);
+  const DType dt = dtype_of(x);
   const int64_t n = x.numel();
   const int64_t bytes =
       buffer_size(n, dt, (int)bits, (int)bucket_size, skip_incomplete);
   auto out = at::zeros({std::max<int64_t>(bytes, 1)},
                        at::TensorOptions().dtype(at::kByte).device(x.device()));
-  if (n == 0) return out;
-
-  struct Blob {
-    QuantDesc d;
-    int64_t cum[2];
-  } hb;
   auto stream =
       c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x.device().index());
-  auto upload = [&](const Blob& blob) {
-    return at::from_blob(const_cast<Blob*>(&blob), {(int64_t)sizeof(Blob)},
-                         at::TensorOptions().dtype(at::kByte))
-        .to(x.device());
-  };
-  const int32_t base_flags = skip_incomplete ? kFlagSkipIncomplete : 0;
-  const bool aligned =
-      (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15) == 0;
-  // mirror the engine's launch split (run_quantize): lean fast kernel for
-  // the full buckets, generic kernel for the partial tail
-  if (bucket_size % 8 == 0 && !fbp && aligned && n >= bucket_size &&
-      bucket_size <= 2048) {  // register-stash limit (4 groups/lane)
-    hb.d = QuantDesc{x.data_ptr(), out.data_ptr<uint8_t>(), nullptr, n,
-                     (int32_t)bucket_size, base_flags};
-    hb.cum[0] = 0;
-    hb.cum[1] = n / bucket_size;
-    auto dev = upload(hb);
+  for (const QuantGroup& g : route_quantize({QuantSlice{
+           x.data_ptr(), out.data_ptr<uint8_t>(), fbp, n, (int)bits,
+           (int)bucket_size, skip_incomplete}})) {
+    auto dev = upload(g.descs, g.cum, x.device());
     const char* devp = static_cast<const char*>(dev.data_ptr());
-    const int64_t ng = bucket_size >> 3;
-    if (ng < 64 && (ng & (ng - 1)) == 0) {
-      launch_quantize_sub(
-          reinterpret_cast<const QuantDesc*>(devp),
-          reinterpret_cast<const int64_t*>(devp + offsetof(Blob, cum)), 1,
-          hb.cum[1], dt, (int)bits, (uint64_t)seed, stochastic,
-          stream.stream(), skip_incomplete && (n % bucket_size) != 0);
-    } else {
-      launch_quantize_fast(
-          reinterpret_cast<const QuantDesc*>(devp),
-          reinterpret_cast<const int64_t*>(devp + offsetof(Blob, cum)), 1,
-          hb.cum[1], dt, (int)bits, (uint64_t)seed, stochastic,
-          stream.stream(), skip_incomplete && (n % bucket_size) != 0,
-          (int)((bucket_size / 8 + 63) / 64));
-    }
-    if (!skip_incomplete && (n % bucket_size) != 0) {
-      Blob tb;
-      tb.d = QuantDesc{x.data_ptr(), out.data_ptr<uint8_t>(), nullptr, n,
-                       (int32_t)bucket_size, base_flags | kFlagTailOnly};
-      tb.cum[0] = 0;
-      tb.cum[1] = 1;
-      auto tdev = upload(tb);
-      const char* tdevp = static_cast<const char*>(tdev.data_ptr());
-      launch_quantize_batch(
-          reinterpret_cast<const QuantDesc*>(tdevp),
-          reinterpret_cast<const int64_t*>(tdevp + offsetof(Blob, cum)), 1, 1,
-          dt, (int)bits, (uint64_t)seed, stochastic, stream.stream(),
-          /*buckets_mult8=*/true, false);
-    }
-    return out;
+    launch(g, reinterpret_cast<const QuantDesc*>(devp),
+           reinterpret_cast<const int64_t*>(devp +
+                                            sizeof(QuantDesc) * g.descs.size()),
+           dt, (uint64_t)seed, stochastic, stream.stream());
   }
-  hb.d = QuantDesc{x.data_ptr(), out.data_ptr<uint8_t>(), fbp, n,
-                   (int32_t)bucket_size, base_flags};
-  hb.cum[0] = 0;
-  hb.cum[1] = skip_incomplete ? n / bucket_size
-                              : (n + bucket_size - 1) / bucket_size;
-  auto dev = upload(hb);
-  const char* devp = static_cast<const char*>(dev.data_ptr());
-  launch_quantize_batch(
-      reinterpret_cast<const QuantDesc*>(devp),
-      reinterpret_cast<const int64_t*>(devp + offsetof(Blob, cum)), 1,
-      hb.cum[1], dt, (int)bits, (uint64_t)seed, stochastic, stream.stream(),
-      bucket_size % 8 == 0,
-      skip_incomplete && (n % bucket_size) != 0);
   return out;
 }
 
@@ -308,56 +281,8 @@ at::Tensor py_quantize(at::Tensor x, int64_t bits, int64_t bucket_size,
 void py_dequantize(at::Tensor comp, at::Tensor out, int64_t bits,
                    int64_t bucket_size, bool add, bool skip_incomplete) {
   TORCH_CHECK(comp.is_cuda() && out.is_cuda() && out.is_contiguous());
-  const DType dt = dtype_arg(out);
-  const int64_t n = out.numel();
-  if (n == 0) return;
-  const int64_t nq =
-      skip_incomplete ? n / bucket_size * bucket_size : n;
-  struct Blob {
-    DequantDesc d;
-    int64_t cum[2];
-  } hb;
-  auto stream =
-      c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(out.device().index());
-  auto upload = [&](const Blob& blob) {
-    return at::from_blob(const_cast<Blob*>(&blob), {(int64_t)sizeof(Blob)},
-                         at::TensorOptions().dtype(at::kByte))
-        .to(out.device());
-  };
-  const int32_t base_flags = skip_incomplete ? kFlagSkipIncomplete : 0;
-  hb.d = DequantDesc{comp.data_ptr<uint8_t>(), out.data_ptr(), n, 0,
-                     (int32_t)bucket_size, 1, add ? 1 : 0, base_flags};
-  hb.cum[0] = 0;
-  hb.cum[1] = (nq + 7) / 8;
-  // mirror the engine's launch split (run_dequant)
-  if (bucket_size % 8 == 0 && nq < (int64_t(1) << 31)) {
-    auto dev = upload(hb);
-    const char* devp = static_cast<const char*>(dev.data_ptr());
-    launch_dequantize_fast(reinterpret_cast<const DequantDesc*>(devp), 1,
-                           hb.cum[1], dt, (int)bits, stream.stream(),
-                           skip_incomplete && (n % bucket_size) != 0);
-    const bool ragged =
-        elem_size(dt) == 4 ? (nq & 3) != 0 : (nq & 7) != 0;
-    if (ragged) {
-      Blob tb = hb;
-      tb.d.flags = base_flags | kFlagTailOnly;
-      tb.cum[1] = 1;
-      auto tdev = upload(tb);
-      const char* tdevp = static_cast<const char*>(tdev.data_ptr());
-      launch_dequantize_batch(
-          reinterpret_cast<const DequantDesc*>(tdevp),
-          reinterpret_cast<const int64_t*>(tdevp + offsetof(Blob, cum)), 1, 1,
-          dt, (int)bits, stream.stream(), false);
-    }
-    return;
-  }
-  auto dev = upload(hb);
-  const char* devp = static_cast<const char*>(dev.data_ptr());
-  launch_dequantize_batch(
-      reinterpret_cast<const DequantDesc*>(devp),
-      reinterpret_cast<const int64_t*>(devp + offsetof(Blob, cum)), 1,
-      hb.cum[1], dt, (int)bits, stream.stream(),
-      skip_incomplete && (n % bucket_size) != 0);
+  dequantize_slice(comp, out, bits, bucket_size, skip_incomplete,
+                   /*src_stride=*/0, /*nsrc=*/1, add);
 }
 
 // Multi-source decode-and-sum: comp is [nsrc, stride] uint8; decodes each
@@ -366,55 +291,69 @@ void py_dequantize_multi(at::Tensor comp, at::Tensor out, int64_t bits,
                          int64_t bucket_size, bool add) {
   TORCH_CHECK(comp.is_cuda() && comp.dim() == 2 && comp.is_contiguous());
   TORCH_CHECK(out.is_cuda() && out.is_contiguous());
-  const DType dt = dtype_arg(out);
-  const int64_t n = out.numel();
-  if (n == 0) return;
-  struct Blob {
-    DequantDesc d;
-    int64_t cum[2];
-  } hb;
-  hb.d = DequantDesc{comp.data_ptr<uint8_t>(), out.data_ptr(), n,
-                     comp.stride(0), (int32_t)bucket_size,
-                     (int32_t)comp.size(0), add ? 1 : 0, 0};
-  hb.cum[0] = 0;
-  hb.cum[1] = (n + 7) / 8;
-  auto dev = at::from_blob(&hb, {(int64_t)sizeof(Blob)},
-                           at::TensorOptions().dtype(at::kByte))
-                 .to(out.device());
-  auto stream =
-      c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(out.device().index());
-  const char* devp = static_cast<const char*>(dev.data_ptr());
-  if (bucket_size % 8 == 0 && n < (int64_t(1) << 31)) {
-    launch_dequantize_fast(reinterpret_cast<const DequantDesc*>(devp), 1,
-                           hb.cum[1], dt, (int)bits, stream.stream());
-    const bool ragged = elem_size(dt) == 4 ? (n & 3) != 0 : (n & 7) != 0;
-    if (ragged) {
-      Blob tb = hb;
-      tb.d.flags = kFlagTailOnly;
-      tb.cum[1] = 1;
-      auto tdev = at::from_blob(&tb, {(int64_t)sizeof(Blob)},
-                                at::TensorOptions().dtype(at::kByte))
-                      .to(out.device());
-      const char* tdevp = static_cast<const char*>(tdev.data_ptr());
-      launch_dequantize_batch(
-          reinterpret_cast<const DequantDesc*>(tdevp),
-          reinterpret_cast<const int64_t*>(tdevp + offsetof(Blob, cum)), 1, 1,
-          dt, (int)bits, stream.stream());
-    }
-    return;
-  }
-  launch_dequantize_batch(
-      reinterpret_cast<const DequantDesc*>(devp),
-      reinterpret_cast<const int64_t*>(devp + offsetof(Blob, cum)), 1,
-      hb.cum[1], dt, (int)bits, stream.stream());
+  dequantize_slice(comp, out, bits, bucket_size, /*skip_incomplete=*/false,
+                   comp.stride(0), (int)comp.size(0), add);
 }
 
 int64_t py_buffer_size(int64_t n, at::ScalarType st, int64_t bits,
                        int64_t bucket_size, bool skip_incomplete) {
-  DType dt = st == at::kFloat ? DType::F32
-             : st == at::kHalf ? DType::F16
-                               : DType::BF16;
-  return buffer_size(n, dt, (int)bits, (int)bucket_size, skip_incomplete);
+  return buffer_size(n, dtype_of(st), (int)bits, (int)bucket_size,
+                     skip_incomplete);
+}
+
+// Test seams for the router (compress.h): pure host code, pointers travel
+// as ints, so the routing policy is testable without a GPU.
+// slices: [(in, out, fb, n, bits, bucket, skip_incomplete)] ->
+// [(bits, kind, [(in, out, fb, n, bucket, flags)], cum, any_residual,
+//   max_gpl)]
+py::list py_route_quantize(
+    const std::vector<std::tuple<uint64_t, uint64_t, uint64_t, int64_t, int,
+                                 int, bool>>& slices) {
+  std::vector<QuantSlice> qs;
+  for (const auto& [in, out, fb, n, bits, bucket, skip] : slices)
+    qs.push_back(QuantSlice{reinterpret_cast<const void*>(in),
+                            reinterpret_cast<uint8_t*>(out),
+                            reinterpret_cast<void*>(fb), n, bits, bucket,
+                            skip});
+  py::list groups;
+  for (const QuantGroup& g : route_quantize(qs)) {
+    py::list descs;
+    for (const QuantDesc& d : g.descs)
+      descs.append(py::make_tuple(reinterpret_cast<uint64_t>(d.in),
+                                  reinterpret_cast<uint64_t>(d.out),
+                                  reinterpret_cast<uint64_t>(d.fb), d.n,
+                                  d.bucket, d.flags));
+    groups.append(py::make_tuple(g.bits, g.kind, descs, g.cum, g.any_residual,
+                                 g.max_gpl));
+  }
+  return groups;
+}
+
+// slices: [(in, out, n, bits, bucket, skip_incomplete)] ->
+// [(bits, kind, [(in, out, n, src_stride, bucket, nsrc, add, flags)],
+//   total_groups, any_residual)]
+py::list py_route_dequantize(
+    const std::vector<std::tuple<uint64_t, uint64_t, int64_t, int, int,
+                                 bool>>& slices,
+    at::ScalarType st, int64_t src_stride, int nsrc, bool add) {
+  std::vector<DequantSlice> ds;
+  for (const auto& [in, out, n, bits, bucket, skip] : slices)
+    ds.push_back(DequantSlice{reinterpret_cast<const uint8_t*>(in),
+                              reinterpret_cast<void*>(out), n, bits, bucket,
+                              skip});
+  py::list groups;
+  for (const DequantGroup& g :
+       route_dequantize(ds, dtype_of(st), src_stride, nsrc, add)) {
+    py::list descs;
+    for (const DequantDesc& d : g.descs)
+      descs.append(py::make_tuple(reinterpret_cast<uint64_t>(d.in),
+                                  reinterpret_cast<uint64_t>(d.out), d.n,
+                                  d.src_stride, d.bucket, d.nsrc, d.add,
+                                  d.flags));
+    groups.append(py::make_tuple(g.bits, g.kind, descs, g.total_groups,
+                                 g.any_residual));
+  }
+  return groups;
 }
 
 std::pair<std::vector<int64_t>, std::vector<int64_t>> py_partition(
@@ -546,4 +485,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bits"), py::arg("bucket_size"),
         py::arg("skip_incomplete") = false);
   m.def("partition", &cgx::py_partition);
+  m.def("route_quantize", &cgx::py_route_quantize, py::arg("slices"),
+        "Test seam: the launch router's quantize plan for "
+        "[(in, out, fb, n, bits, bucket, skip_incomplete)] (pointers as "
+        "ints) -> [(bits, kind, descs, cum, any_residual, max_gpl)].");
+  m.def("route_dequantize", &cgx::py_route_dequantize, py::arg("slices"),
+        py::arg("dtype"), py::arg("src_stride") = 0, py::arg("nsrc") = 1,
+        py::arg("add") = false,
+        "Test seam: the launch router's dequantize plan for "
+        "[(in, out, n, bits, bucket, skip_incomplete)] -> "
+        "[(bits, kind, descs, total_groups, any_residual)].");
+  m.attr("FLAG_SKIP_INCOMPLETE") = cgx::kFlagSkipIncomplete;
+  m.attr("FLAG_TAIL_ONLY") = cgx::kFlagTailOnly;
+  m.attr("KIND_FAST") = (int)cgx::kFast;
+  m.attr("KIND_GENERIC") = (int)cgx::kGeneric;
+  m.attr("KIND_TWO_PASS") = (int)cgx::kTwoPass;
+  m.attr("KIND_SUB") = (int)cgx::kSub;
 }

@@ -11,6 +11,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace cgx {
 
@@ -18,28 +19,49 @@ enum class DType : int { F32 = 0, F16 = 1, BF16 = 2 };
 
 inline int elem_size(DType d) { return d == DType::F32 ? 4 : 2; }
 
-inline int64_t align8(int64_t x) { return (x + 7) / 8 * 8; }
+__host__ __device__ inline int64_t align8(int64_t x) {
+  return (x + 7) / 8 * 8;
+}
 
-// Compressed byte size of an n-element slice (golden.buffer_size parity).
+// Wire layout of one n-element slice; the one place it is computed, for
+// buffer_size(), the router and every kernel.
 // skip_incomplete: the trailing partial bucket is stored as raw T values
 // after the aligned packed region instead of being quantized.
+struct SliceGeom {
+  int64_t nq;            // quantized elements (== n unless skip_incomplete)
+  int64_t nb;            // buckets with a (unit, min) pair
+  int64_t meta_bytes;    // 2 * nb * esize; the packed region starts here
+  int64_t packed_bytes;  // ceil(nq * bits / 8): bytes the packs occupy
+  int64_t resid_off;     // byte offset of the raw residual tail
+  int64_t resid;         // raw residual elements (n - nq)
+};
+
+__host__ __device__ inline SliceGeom slice_geom(int64_t n, int bucket,
+                                                int bits, int esize,
+                                                bool skip_incomplete) {
+  SliceGeom g;
+  g.nq = skip_incomplete ? (n / bucket) * static_cast<int64_t>(bucket) : n;
+  g.nb = skip_incomplete ? n / bucket : (n + bucket - 1) / bucket;
+  g.meta_bytes = 2 * static_cast<int64_t>(esize) * g.nb;
+  g.packed_bytes = (g.nq * bits + 7) / 8;
+  g.resid_off = g.meta_bytes + align8(g.packed_bytes);
+  g.resid = n - g.nq;
+  return g;
+}
+
+// Compressed byte size of an n-element slice (golden.buffer_size parity).
 inline int64_t buffer_size(int64_t n, DType dt, int bits, int bucket_size,
                            bool skip_incomplete = false) {
   if (n == 0) return 0;
-  int64_t nb = (n + bucket_size - 1) / bucket_size;
-  int64_t residuals = 0;
-  if (skip_incomplete) {
-    nb = n / bucket_size;
-    residuals = n % bucket_size;
-    n = nb * bucket_size;
-  }
-  return 2 * nb * elem_size(dt) + align8((n * bits + 7) / 8) +
-         residuals * elem_size(dt);
+  const SliceGeom g =
+      slice_geom(n, bucket_size, bits, elem_size(dt), skip_incomplete);
+  return g.resid_off + g.resid * elem_size(dt);
 }
 
 constexpr int32_t kFlagSkipIncomplete = 1;
-// The slice's full buckets were already quantized by the lean fast kernel;
-// this (generic-kernel) desc covers only the trailing partial bucket.
+// The slice's full buckets (quantize) or full 4/8-element units (dequant)
+// were already handled by the lean fast kernel; this generic-kernel desc
+// covers only the trailing partial bucket / ragged tail.
 constexpr int32_t kFlagTailOnly = 2;
 
 // One quantize work item: compress `n` elems at `in` into `out` bytes.
@@ -53,7 +75,7 @@ struct QuantDesc {
   void* fb;
   int64_t n;
   int32_t bucket;
-  int32_t flags;  // kFlagSkipIncomplete
+  int32_t flags;  // kFlagSkipIncomplete | kFlagTailOnly
 };
 
 // One dequantize work item: decode `n` elems from `nsrc` compressed streams
@@ -67,56 +89,90 @@ struct DequantDesc {
   int32_t bucket;
   int32_t nsrc;
   int32_t add;
-  int32_t flags;  // kFlagSkipIncomplete
+  int32_t flags;  // kFlagSkipIncomplete | kFlagTailOnly
 };
 
-// Batched launchers. descs/cum live in DEVICE memory. `cum` is the exclusive
-// prefix over per-slice work-unit counts with a trailing total:
-//   quantize: work unit = bucket,     cum[i+1]-cum[i] = ceil(n_i/bucket_i)
-//   dequant:  work unit = 8-elem group, cum[i+1]-cum[i] = ceil(n_i/8)
-// All slices in one launch share `bits` (the engine groups by bits).
-// buckets_mult8: caller guarantees every slice's bucket_size % 8 == 0 (the
-// fused single-read path); otherwise a meta pass + generic pack pass run.
-// any_residual: at least one slice carries kFlagSkipIncomplete with a
-// non-empty raw residual tail (adds one small copy/accumulate pass).
-void launch_quantize_batch(const QuantDesc* descs, const int64_t* cum,
-                           int nslices, int64_t total_buckets, DType dt,
-                           int bits, uint64_t seed, bool stochastic,
-                           hipStream_t stream, bool buckets_mult8,
-                           bool any_residual = false);
+// ---------------------------------------------------------------------------
+// Router: the one place that decides which kernel serves which slice.
+//
+// The kernel family is split into register-isolated launches (see
+// quant_kernels.hip); route_quantize/route_dequantize sort a list of slices
+// into launch groups, in ascending (bits, kind) order, slices in input order
+// inside a group.  Pure host code: no HIP calls.  The caller copies
+// descs (and, for quantize, cum) to the device and hands them to launch().
+// ---------------------------------------------------------------------------
+enum LaunchKind : int {
+  // quantize: bucket % 8 == 0, bucket <= 2048 (the register stash), 16B
+  //   aligned input, no error feedback, n >= bucket.  cum counts FULL
+  //   buckets; a partial last bucket re-enters kGeneric with kFlagTailOnly
+  //   (unless skip_incomplete, where it travels raw).
+  // dequant: bucket % 8 == 0 and nq < 2^31 (u32 indexing; per-thread
+  //   indices are 4/8-element units).  A ragged tail (nq % 4 for fp32,
+  //   nq % 8 for 16-bit) re-enters kGeneric with kFlagTailOnly.
+  kFast = 0,
+  // everything else with bucket % 8 == 0: error feedback, unaligned input,
+  // n < bucket, bucket > 2048, tails.  cum counts ceil-buckets (1 per tail).
+  kGeneric = 1,
+  // quantize only, bucket % 8 != 0: meta pass + generic pack pass.
+  kTwoPass = 2,
+  // quantize only: kFast's preconditions and bucket/8 a power of two < 64;
+  // the wave packs 64/(bucket/8) buckets per iteration.
+  kSub = 3,
+};
 
-// Lean fast-path kernel: every slice has bucket % 8 == 0, a 16B-aligned
-// input base, no error feedback; cum counts FULL buckets per slice (the
-// partial tail travels through launch_quantize_batch with kFlagTailOnly).
-// Separate launch so its register footprint (and thus occupancy) is not
-// inflated by the generic/EF code paths.
-// max_gpl: max over slices of ceil((bucket/8)/64) — <=2 selects the
-// half-stash kernel variant (higher occupancy for buckets <= 1024).
-void launch_quantize_fast(const QuantDesc* descs, const int64_t* cum,
-                          int nslices, int64_t total_buckets, DType dt,
-                          int bits, uint64_t seed, bool stochastic,
-                          hipStream_t stream, bool any_residual = false,
-                          int max_gpl = 4);
+struct QuantSlice {
+  const void* in;
+  uint8_t* out;
+  void* fb;  // error-feedback residual for this slice, or nullptr
+  int64_t n;
+  int bits;
+  int bucket;
+  bool skip_incomplete;
+};
 
-// Small-bucket variant of the fast kernel: every slice has bucket/8 a
-// power of two < 64; the wave packs 64/(bucket/8) buckets per iteration
-// (segmented DPP reductions).  Separate kernel for register isolation.
-void launch_quantize_sub(const QuantDesc* descs, const int64_t* cum,
-                         int nslices, int64_t total_buckets, DType dt,
-                         int bits, uint64_t seed, bool stochastic,
-                         hipStream_t stream, bool any_residual = false);
+struct DequantSlice {
+  const uint8_t* in;
+  void* out;
+  int64_t n;
+  int bits;
+  int bucket;
+  bool skip_incomplete;
+};
 
-void launch_dequantize_batch(const DequantDesc* descs, const int64_t* cum,
-                             int nslices, int64_t total_groups, DType dt,
-                             int bits, hipStream_t stream,
-                             bool any_residual = false);
+struct QuantGroup {
+  int bits;
+  int kind;
+  std::vector<QuantDesc> descs;
+  // exclusive prefix over per-desc bucket counts, trailing total
+  std::vector<int64_t> cum;
+  // a slice carries kFlagSkipIncomplete with a non-empty raw residual tail
+  // (adds one small copy pass)
+  bool any_residual = false;
+  // kFast: max over slices of ceil((bucket/8)/64); <= 2 selects the
+  // half-stash kernel variant (higher occupancy for buckets <= 1024)
+  int max_gpl = 1;
+};
 
-// Lean dequant kernel: every slice has bucket % 8 == 0 and fits u32
-// indexing (n < 2^31; per-thread indices are 4/8-element units); ragged tails (n % 4 fp32 / n % 8 16-bit) re-enter
-// launch_dequantize_batch with kFlagTailOnly.
-void launch_dequantize_fast(const DequantDesc* descs, int nslices,
-                            int64_t total_groups, DType dt, int bits,
-                            hipStream_t stream, bool any_residual = false);
+struct DequantGroup {
+  int bits;
+  int kind;
+  std::vector<DequantDesc> descs;
+  int64_t total_groups = 0;  // 8-element groups of work: sizes the grid
+  bool any_residual = false;
+};
+
+// Slices with n <= 0 are dropped.
+std::vector<QuantGroup> route_quantize(const std::vector<QuantSlice>& slices);
+std::vector<DequantGroup> route_dequantize(
+    const std::vector<DequantSlice>& slices, DType dt, int64_t src_stride,
+    int nsrc, bool add);
+
+// Launch one group; `descs`/`cum` are the DEVICE copies of g.descs/g.cum.
+// The stochastic hash key is (index in group << 44) | pack index.
+void launch(const QuantGroup& g, const QuantDesc* descs, const int64_t* cum,
+            DType dt, uint64_t seed, bool stochastic, hipStream_t stream);
+void launch(const DequantGroup& g, const DequantDesc* descs, DType dt,
+            hipStream_t stream);
 
 // y[i] += x[i] elementwise (T precision), n elements.
 void launch_add(const void* x, void* y, int64_t n, DType dt,

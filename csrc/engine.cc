@@ -8,7 +8,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <map>
+#include <initializer_list>
 
 namespace cgx {
 
@@ -197,14 +197,25 @@ void* DescRing::commit(size_t bytes, hipStream_t stream) {
 // ---------------------------------------------------------------------------
 // dtype maps
 // ---------------------------------------------------------------------------
-DType dtype_of(const at::Tensor& t) {
-  switch (t.scalar_type()) {
+DType dtype_of(at::ScalarType st) {
+  switch (st) {
     case at::kFloat: return DType::F32;
     case at::kHalf: return DType::F16;
     case at::kBFloat16: return DType::BF16;
     default:
-      TORCH_CHECK(false, "cgx: unsupported compression dtype ", t.scalar_type());
+      TORCH_CHECK(false, "cgx: unsupported compression dtype ", st);
   }
+}
+
+DType dtype_of(const at::Tensor& t) { return dtype_of(t.scalar_type()); }
+
+at::ScalarType scalar_type_of(DType dt) {
+  switch (dt) {
+    case DType::F32: return at::kFloat;
+    case DType::F16: return at::kHalf;
+    case DType::BF16: return at::kBFloat16;
+  }
+  TORCH_CHECK(false, "cgx: invalid DType ", (int)dt);
 }
 
 ncclDataType_t nccl_dtype(const at::Tensor& t) {
@@ -257,31 +268,40 @@ Engine::~Engine() {
   }
 }
 
+void Engine::timer_collect(int slot) {
+  // the slot's last event has completed: fold its phase times into the sums
+  PhaseTimer& t = timer_;
+  for (int p = 0; p + 1 < PhaseTimer::kEv; p++) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, t.ev[slot][p], t.ev[slot][p + 1]) ==
+        hipSuccess)
+      t.sum_ms[p] += ms;
+  }
+  t.count++;
+  t.pending[slot] = false;
+}
+
+void Engine::timer_print(const char* suffix) const {
+  const PhaseTimer& t = timer_;
+  fprintf(stderr,
+          "[cgx timings rank %d, %lld chunks%s] quantize %.3f ms | "
+          "comm1 %.3f | decode+requant %.3f | comm2 %.3f | decode2 %.3f\n",
+          rank_, (long long)t.count, suffix, t.sum_ms[0] / t.count,
+          t.sum_ms[1] / t.count, t.sum_ms[2] / t.count,
+          t.sum_ms[3] / t.count, t.sum_ms[4] / t.count);
+}
+
 void Engine::timer_drain() {
   // collect any in-flight timing slots and print the final averages (short
   // runs would otherwise never reach the 50-chunk periodic print)
   PhaseTimer& t = timer_;
   if (!t.inited) return;
   for (int r = 0; r < PhaseTimer::kRing; r++) {
-    if (!t.pending[r]) continue;
-    if (hipEventSynchronize(t.ev[r][PhaseTimer::kEv - 1]) != hipSuccess)
-      continue;
-    for (int p = 0; p + 1 < PhaseTimer::kEv; p++) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, t.ev[r][p], t.ev[r][p + 1]) == hipSuccess)
-        t.sum_ms[p] += ms;
-    }
-    t.count++;
-    t.pending[r] = false;
+    if (t.pending[r] &&
+        hipEventSynchronize(t.ev[r][PhaseTimer::kEv - 1]) == hipSuccess)
+      timer_collect(r);
   }
-  if (t.count > 0) {
-    fprintf(stderr,
-            "[cgx timings rank %d, %lld chunks total] quantize %.3f ms | "
-            "comm1 %.3f | decode+requant %.3f | comm2 %.3f | decode2 %.3f\n",
-            rank_, (long long)t.count, t.sum_ms[0] / t.count,
-            t.sum_ms[1] / t.count, t.sum_ms[2] / t.count,
-            t.sum_ms[3] / t.count, t.sum_ms[4] / t.count);
-  }
+  if (t.count > 0) timer_print(" total");
 }
 
 hipEvent_t Engine::next_ev() {
@@ -330,53 +350,37 @@ void Engine::partition(int64_t num_elements, int ws,
   }
 }
 
-uint8_t* Engine::staging(int64_t bytes, hipStream_t user) {
+// Grow `buf` to at least `bytes` (power-of-two capacity).  The old buffer
+// may still be read by work queued on `streams`; the caching allocator
+// defers its reuse until those streams pass.
+static uint8_t* grow(at::Tensor& buf, int64_t bytes,
+                     std::initializer_list<hipStream_t> streams) {
   if (bytes <= 0) bytes = 1;
-  if (!staging_.defined() || staging_.numel() < bytes) {
-    if (staging_.defined()) {
-      // the old buffer may still be read by queued work on the user/comm/deq
-      // streams; let the caching allocator defer reuse past those streams
-      for (hipStream_t s : {user, comm_stream_, deq_stream_}) {
+  if (!buf.defined() || buf.numel() < bytes) {
+    if (buf.defined()) {
+      for (hipStream_t s : streams) {
         if (!s) continue;
         c10::hip::HIPCachingAllocatorMasqueradingAsCUDA::
             recordStreamMasqueradingAsCUDA(
-                staging_.storage().data_ptr(),
+                buf.storage().data_ptr(),
                 c10::hip::getStreamFromExternalMasqueradingAsCUDA(
-                    s, staging_.device().index()));
+                    s, buf.device().index()));
       }
     }
     int64_t cap = 1 << 20;
     while (cap < bytes) cap *= 2;
-    staging_ = at::empty({cap}, at::TensorOptions()
-                                    .dtype(at::kByte)
-                                    .device(at::kCUDA));
+    buf = at::empty({cap},
+                    at::TensorOptions().dtype(at::kByte).device(at::kCUDA));
   }
-  return staging_.data_ptr<uint8_t>();
+  return buf.data_ptr<uint8_t>();
+}
+
+uint8_t* Engine::staging(int64_t bytes, hipStream_t user) {
+  return grow(staging_, bytes, {user, comm_stream_, deq_stream_});
 }
 
 uint8_t* Engine::slot_bytes(StagingSlot& slot, int64_t bytes) {
-  if (bytes <= 0) bytes = 1;
-  if (!slot.buf.defined() || slot.buf.numel() < bytes) {
-    if (slot.buf.defined()) {
-      // the old buffer may still be referenced by in-flight comm/deq work;
-      // let the caching allocator defer reuse until those streams pass
-      auto rec = [&](hipStream_t s) {
-        c10::hip::HIPCachingAllocatorMasqueradingAsCUDA::
-            recordStreamMasqueradingAsCUDA(
-                slot.buf.storage().data_ptr(),
-                c10::hip::getStreamFromExternalMasqueradingAsCUDA(
-                    s, slot.buf.device().index()));
-      };
-      rec(comm_stream_);
-      rec(deq_stream_);
-    }
-    int64_t cap = 1 << 20;
-    while (cap < bytes) cap *= 2;
-    slot.buf = at::empty({cap}, at::TensorOptions()
-                                    .dtype(at::kByte)
-                                    .device(at::kCUDA));
-  }
-  return slot.buf.data_ptr<uint8_t>();
+  return grow(slot.buf, bytes, {comm_stream_, deq_stream_});
 }
 
 at::Tensor& Engine::feedback_buf(int64_t key, int phase, int64_t numel,
@@ -408,18 +412,8 @@ at::Tensor& Engine::feedback_buf(int64_t key, int phase, int64_t numel,
 void Engine::run_quantize(const std::vector<Slice>& slices, uint8_t* out_base,
                           DType dt, hipStream_t stream, bool stochastic,
                           char* fb_base, int64_t fb_rebase) {
-  // Three launch kinds per bits value:
-  //   0 = lean fast kernel (bucket%8==0, 16B-aligned input, no error
-  //       feedback, >=1 full bucket) — low register footprint, cum counts
-  //       FULL buckets; a partial tail re-enters kind 1 with kFlagTailOnly
-  //   1 = generic fused kernel (EF, unaligned, tails)
-  //   2 = meta + pack two-pass (bucket%8 != 0)
-  struct Ent {
-    const Slice* s;
-    void* fb;
-    int32_t flags;
-  };
-  std::map<std::pair<int, int>, std::vector<Ent>> groups;
+  std::vector<QuantSlice> qs;
+  qs.reserve(slices.size());
   for (const auto& s : slices) {
     if (s.n <= 0) continue;
     void* fb =
@@ -428,138 +422,37 @@ void Engine::run_quantize(const std::vector<Slice>& slices, uint8_t* out_base,
                 "cgx: error-feedback slice offset below buffer base");
     TORCH_CHECK(!fb || s.bucket % 8 == 0,
                 "cgx: CGX_ERROR_FEEDBACK requires bucket_size % 8 == 0");
-    const int32_t flags = s.skip_incomplete ? kFlagSkipIncomplete : 0;
-    if ((s.bucket % 8) != 0) {
-      groups[{s.bits, 2}].push_back(Ent{&s, fb, flags});
-      continue;
-    }
-    const bool aligned = (reinterpret_cast<uintptr_t>(s.data) & 15) == 0;
-    // bucket <= 2048: whole bucket fits the register stash (4 groups/lane);
-    // small power-of-two buckets (bucket < 512) pack several buckets per
-    // wave in their own kernel (kind 3, QuantSub)
-    if (!fb && aligned && s.n >= s.bucket && s.bucket <= 2048) {
-      const int ng = s.bucket >> 3;
-      const bool small_pow2 = ng < 64 && (ng & (ng - 1)) == 0;
-      groups[{s.bits, small_pow2 ? 3 : 0}].push_back(Ent{&s, nullptr, flags});
-      if (!s.skip_incomplete && (s.n % s.bucket) != 0)
-        groups[{s.bits, 1}].push_back(Ent{&s, nullptr,
-                                          flags | kFlagTailOnly});
-    } else {
-      groups[{s.bits, 1}].push_back(Ent{&s, fb, flags});
-    }
+    qs.push_back(QuantSlice{s.data, out_base + s.comp_off, fb, s.n, s.bits,
+                            s.bucket, s.skip_incomplete});
   }
-  for (auto& [key, list] : groups) {
-    const auto [bits, kind] = key;
-    const int nsl = (int)list.size();
-    const size_t desc_bytes = sizeof(QuantDesc) * nsl;
-    const size_t cum_bytes = sizeof(int64_t) * (nsl + 1);
+  for (const QuantGroup& g : route_quantize(qs)) {
+    const size_t desc_bytes = sizeof(QuantDesc) * g.descs.size();
+    const size_t cum_bytes = sizeof(int64_t) * g.cum.size();
     char* host = (char*)ring_.acquire(desc_bytes + cum_bytes);
-    auto* qd = reinterpret_cast<QuantDesc*>(host);
-    auto* cum = reinterpret_cast<int64_t*>(host + desc_bytes);
-    cum[0] = 0;
-    bool any_residual = false;
-    for (int i = 0; i < nsl; i++) {
-      const Slice& s = *list[i].s;
-      qd[i] = QuantDesc{s.data, out_base + s.comp_off, list[i].fb, s.n,
-                        s.bucket, list[i].flags};
-      int64_t nb;
-      if (kind == 0 || kind == 3) {
-        nb = s.n / s.bucket;  // full buckets only
-        any_residual |= s.skip_incomplete && (s.n % s.bucket) != 0;
-      } else if (list[i].flags & kFlagTailOnly) {
-        nb = 1;
-      } else if (s.skip_incomplete) {
-        nb = s.n / s.bucket;
-        any_residual |= (s.n % s.bucket) != 0;
-      } else {
-        nb = (s.n + s.bucket - 1) / s.bucket;
-      }
-      cum[i + 1] = cum[i] + nb;
-    }
+    std::memcpy(host, g.descs.data(), desc_bytes);
+    std::memcpy(host + desc_bytes, g.cum.data(), cum_bytes);
     char* dev = (char*)ring_.commit(desc_bytes + cum_bytes, stream);
-    auto* ddesc = reinterpret_cast<QuantDesc*>(dev);
-    auto* dcum = reinterpret_cast<int64_t*>(dev + desc_bytes);
-    if (kind == 3) {
-      launch_quantize_sub(ddesc, dcum, nsl, cum[nsl], dt, bits, seed_++,
-                          stochastic, stream, any_residual);
-    } else if (kind == 0) {
-      int max_gpl = 1;
-      for (const auto& e : list)
-        max_gpl = std::max(max_gpl,
-                           ((e.s->bucket >> 3) + 63) >> 6);
-      launch_quantize_fast(ddesc, dcum, nsl, cum[nsl], dt, bits, seed_++,
-                           stochastic, stream, any_residual, max_gpl);
-    } else {
-      launch_quantize_batch(ddesc, dcum, nsl, cum[nsl], dt, bits, seed_++,
-                            stochastic, stream, /*buckets_mult8=*/kind == 1,
-                            any_residual);
-    }
+    launch(g, reinterpret_cast<const QuantDesc*>(dev),
+           reinterpret_cast<const int64_t*>(dev + desc_bytes), dt, seed_++,
+           stochastic, stream);
   }
 }
 
 void Engine::run_dequant(const std::vector<Slice>& slices,
                          const uint8_t* in_base, int64_t src_stride, int nsrc,
                          bool add, DType dt, hipStream_t stream) {
-  // kind 0: lean fast kernel (bucket%8==0, u32-indexable); a ragged tail
-  // re-enters kind 1 with kFlagTailOnly.  kind 1: generic kernel.
-  struct Ent {
-    const Slice* s;
-    int32_t flags;
-  };
-  const int es = elem_size(dt);
-  std::map<std::pair<int, int>, std::vector<Ent>> groups;
-  for (const auto& s : slices) {
-    if (s.n <= 0) continue;
-    const int32_t flags = s.skip_incomplete ? kFlagSkipIncomplete : 0;
-    const int64_t nq =
-        s.skip_incomplete ? s.n / s.bucket * (int64_t)s.bucket : s.n;
-    const bool fast = (s.bucket % 8) == 0 && nq < (int64_t(1) << 31);
-    if (fast) {
-      groups[{s.bits, 0}].push_back(Ent{&s, flags});
-      const bool ragged = es == 4 ? (nq & 3) != 0 : (nq & 7) != 0;
-      if (ragged)
-        groups[{s.bits, 1}].push_back(Ent{&s, flags | kFlagTailOnly});
-    } else {
-      groups[{s.bits, 1}].push_back(Ent{&s, flags});
-    }
-  }
-  for (auto& [key, list] : groups) {
-    const auto [bits, kind] = key;
-    const int nsl = (int)list.size();
-    const size_t desc_bytes = sizeof(DequantDesc) * nsl;
-    const size_t cum_bytes = sizeof(int64_t) * (nsl + 1);
-    char* host = (char*)ring_.acquire(desc_bytes + cum_bytes);
-    auto* dd = reinterpret_cast<DequantDesc*>(host);
-    auto* cum = reinterpret_cast<int64_t*>(host + desc_bytes);
-    cum[0] = 0;
-    bool any_residual = false;
-    for (int i = 0; i < nsl; i++) {
-      const Slice& s = *list[i].s;
-      dd[i] = DequantDesc{in_base + s.comp_off, s.data,    s.n, src_stride,
-                          s.bucket,             nsrc, add ? 1 : 0,
-                          list[i].flags};
-      int64_t work;
-      if (list[i].flags & kFlagTailOnly) {
-        work = 1;
-      } else if (s.skip_incomplete) {
-        const int64_t nq = s.n / s.bucket * (int64_t)s.bucket;
-        work = (nq + 7) / 8;
-        any_residual |= (s.n % s.bucket) != 0;
-      } else {
-        work = (s.n + 7) / 8;
-      }
-      cum[i + 1] = cum[i] + work;
-    }
-    char* dev = (char*)ring_.commit(desc_bytes + cum_bytes, stream);
-    auto* ddesc = reinterpret_cast<DequantDesc*>(dev);
-    auto* dcum = reinterpret_cast<int64_t*>(dev + desc_bytes);
-    if (kind == 0) {
-      launch_dequantize_fast(ddesc, nsl, cum[nsl], dt, bits, stream,
-                             any_residual);
-    } else {
-      launch_dequantize_batch(ddesc, dcum, nsl, cum[nsl], dt, bits, stream,
-                              any_residual);
-    }
+  std::vector<DequantSlice> ds;
+  ds.reserve(slices.size());
+  for (const auto& s : slices)
+    ds.push_back(DequantSlice{in_base + s.comp_off, s.data, s.n, s.bits,
+                              s.bucket, s.skip_incomplete});
+  for (const DequantGroup& g :
+       route_dequantize(ds, dt, src_stride, nsrc, add)) {
+    const size_t desc_bytes = sizeof(DequantDesc) * g.descs.size();
+    void* host = ring_.acquire(desc_bytes);
+    std::memcpy(host, g.descs.data(), desc_bytes);
+    launch(g, static_cast<const DequantDesc*>(ring_.commit(desc_bytes, stream)),
+           dt, stream);
   }
 }
 
@@ -613,23 +506,8 @@ void Engine::timer_begin(hipStream_t qs, bool enabled) {
   t.cur = (t.cur + 1) % PhaseTimer::kRing;
   if (t.pending[slot]) {
     if (hipEventQuery(t.ev[slot][PhaseTimer::kEv - 1]) == hipSuccess) {
-      for (int p = 0; p + 1 < PhaseTimer::kEv; p++) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, t.ev[slot][p], t.ev[slot][p + 1]) ==
-            hipSuccess)
-          t.sum_ms[p] += ms;
-      }
-      t.count++;
-      if (t.count % 50 == 0) {
-        fprintf(stderr,
-                "[cgx timings rank %d, %lld chunks] quantize %.3f ms | "
-                "comm1 %.3f | decode+requant %.3f | comm2 %.3f | decode2 "
-                "%.3f\n",
-                rank_, (long long)t.count, t.sum_ms[0] / t.count,
-                t.sum_ms[1] / t.count, t.sum_ms[2] / t.count,
-                t.sum_ms[3] / t.count, t.sum_ms[4] / t.count);
-      }
-      t.pending[slot] = false;
+      timer_collect(slot);
+      if (t.count % 50 == 0) timer_print("");
     } else {
       timing_ = false;  // ring full of in-flight chunks: skip this one
       return;
@@ -701,9 +579,7 @@ void Engine::sra_chunk(const std::vector<LayerView>& views, DType dt,
     char* fb1 = nullptr;
     if (cfg.error_feedback) {
       at::Tensor& t =
-          feedback_buf(fb_key, /*phase=*/1, pl.n,
-                       dt == DType::F32 ? at::kFloat
-                       : dt == DType::F16 ? at::kHalf : at::kBFloat16);
+          feedback_buf(fb_key, /*phase=*/1, pl.n, scalar_type_of(dt));
       fb1 = static_cast<char*>(t.data_ptr());
     }
     run_quantize(all, send1, dt, qs, cfg.stochastic, fb1);
@@ -734,10 +610,8 @@ void Engine::sra_chunk(const std::vector<LayerView>& views, DType dt,
     char* fb2 = nullptr;
     int64_t fb2_rebase = 0;
     if (cfg.error_feedback && pl.szs[rank_] > 0) {
-      at::Tensor& t =
-          feedback_buf(fb_key, /*phase=*/2, pl.szs[rank_],
-                       dt == DType::F32 ? at::kFloat
-                       : dt == DType::F16 ? at::kHalf : at::kBFloat16);
+      at::Tensor& t = feedback_buf(fb_key, /*phase=*/2, pl.szs[rank_],
+                                   scalar_type_of(dt));
       // slice fb_off is in chunk element space; the phase-2 buffer covers
       // only this rank's partition, so rebase by its start (host-side per
       // slice — no out-of-range pointer arithmetic)

@@ -234,7 +234,8 @@ class Engine {
   void chain(hipStream_t from, hipStream_t to);  // event: `to` waits `from`
   hipEvent_t next_ev();
 
-  // Launch one quantize "job list", grouping slices by (bits, bucket%8==0).
+  // Launch one quantize "job list": the router (compress.h) sorts the slices
+  // into launch groups, each consuming one seed.
   // fb_base (optional): error-feedback buffer indexed by slice fb_off minus
   // fb_rebase elements (phase 2 buffers cover only this rank's partition, so
   // its slices rebase by the partition start — computed host-side per slice,
@@ -271,6 +272,8 @@ class Engine {
   void timer_mark(int idx, hipStream_t stream);  // idx 1..5
   void timer_finish();
   void timer_drain();  // destructor: flush in-flight slots + final print
+  void timer_collect(int slot);  // fold one finished slot into the sums
+  void timer_print(const char* suffix) const;  // the five-phase line
   bool timing_ = false;
   int timer_slot_ = -1;
 
@@ -288,7 +291,9 @@ class Engine {
   uint64_t seed_;
 };
 
+DType dtype_of(at::ScalarType st);
 DType dtype_of(const at::Tensor& t);
+at::ScalarType scalar_type_of(DType dt);
 ncclDataType_t nccl_dtype(const at::Tensor& t);
 
 }  // namespace cgx

@@ -17,7 +17,12 @@
 //                        meta pass)
 //      k_dequant_fast   (56/33 VGPR; branch-free, incremental bucket index)
 //      k_dequant        (generic + ragged tails via kFlagTailOnly)
-//    The host (engine.cc run_quantize/run_dequant, bindings) routes slices.
+//    The host router (compress.h route_quantize/route_dequantize) decides
+//    which kernel serves which slice; launch() at the end of this file
+//    dispatches a routed group.
+//  * the numeric spec lives once: slice_geom (compress.h) for the wire
+//    layout, quant_level/encode_pack for encode, decode_raw/accum_raw for
+//    decode; every kernel inlines these.
 //  * memory-bound workload: 16-byte vectorized loads/stores wherever the
 //    slice base is 16B-aligned; decode uses 4 elems/thread for fp32 so every
 //    store is one coalesced float4; no integer division or per-access
@@ -58,6 +63,16 @@ __device__ __forceinline__ uint64_t rand_pack(uint64_t seed, uint64_t key) {
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
+}
+
+// The random word of one pack: keyed by the slice's index in its launch
+// group and the pack's index in the slice (0 when rounding is deterministic).
+__device__ __forceinline__ uint64_t pack_rand(uint64_t seed, int stochastic,
+                                              int slice_idx, int64_t pack) {
+  return stochastic
+             ? rand_pack(seed, (static_cast<uint64_t>(slice_idx) << 44) |
+                                   static_cast<uint64_t>(pack))
+             : 0;
 }
 
 __device__ __forceinline__ float rand_lane(uint64_t pack_rand, int j) {
@@ -156,6 +171,107 @@ __device__ __forceinline__ uint32_t f2raw<__half>(float f) {
 template <>
 __device__ __forceinline__ uint32_t f2raw<__hip_bfloat16>(float f) {
   return bitcast<uint16_t>(__float2bfloat16(f));
+}
+
+// ---------------------------------------------------------------------------
+// The numeric spec, one copy each (docs/DESIGN.md "Numerics").
+// ---------------------------------------------------------------------------
+// 8 levels fit a uint32 when BITS <= 4: halves the shift/or cost
+template <int BITS>
+using pack_acc_t =
+    typename std::conditional<(BITS <= 4), uint32_t, uint64_t>::type;
+
+// Quantization level of one element; rnd is 0.5 (deterministic) or uniform
+// in [0,1) (stochastic).
+template <typename T>
+__device__ __forceinline__ uint32_t quant_level(uint32_t raw, float minf,
+                                                float rinv, float rnd,
+                                                float divisor) {
+  const float dd = (raw2f<T>(raw) - minf) * rinv + rnd;
+  return static_cast<uint32_t>(fminf(floorf(dd), divisor));
+}
+
+template <int BITS, typename Acc>
+__device__ __forceinline__ Acc level_bits(uint32_t level, int j) {
+  return static_cast<Acc>(level & ((1u << BITS) - 1)) << (j * BITS);
+}
+
+// Encode one full pack: 8 raw values -> packed word.  pr is the pack's
+// random word (rand_pack), read only when stochastic.
+template <typename T, int BITS, typename Acc = pack_acc_t<BITS>>
+__device__ __forceinline__ Acc encode_pack(const uint32_t (&r)[8], float minf,
+                                           float rinv, float divisor,
+                                           uint64_t pr, int stochastic) {
+  Acc value = 0;
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    const float rnd = stochastic ? rand_lane(pr, j) : 0.5f;
+    value |= level_bits<BITS, Acc>(
+        quant_level<T>(r[j], minf, rinv, rnd, divisor), j);
+  }
+  return value;
+}
+
+// Partial pack (first m <= 8 values); also returns the levels, which the
+// error-feedback residual needs.
+template <typename T, int BITS>
+__device__ __forceinline__ uint64_t encode_pack(const uint32_t (&r)[8], int m,
+                                                float minf, float rinv,
+                                                float divisor, uint64_t pr,
+                                                int stochastic,
+                                                uint32_t (&lv)[8]) {
+  uint64_t value = 0;
+  for (int j = 0; j < m; j++) {
+    const float rnd = stochastic ? rand_lane(pr, j) : 0.5f;
+    lv[j] = quant_level<T>(r[j], minf, rinv, rnd, divisor);
+    value |= level_bits<BITS, uint64_t>(lv[j], j);
+  }
+  return value;
+}
+
+template <int BITS>
+__device__ __forceinline__ uint32_t pack_level(uint64_t value, int j) {
+  return static_cast<uint32_t>((value >> (j * BITS)) & ((1u << BITS) - 1));
+}
+
+// Decode: round(unit*lvl) then round(min + product), both to T.
+template <typename T>
+__device__ __forceinline__ uint32_t decode_raw(uint32_t unit_raw,
+                                               uint32_t min_raw,
+                                               uint32_t lvl) {
+  const uint32_t prod =
+      f2raw<T>(raw2f<T>(unit_raw) * static_cast<float>(lvl));
+  return f2raw<T>(raw2f<T>(min_raw) + raw2f<T>(prod));
+}
+
+// T-precision accumulate in source order; the first source of a non-adding
+// decode just lands.
+template <typename T>
+__device__ __forceinline__ void accum_raw(uint32_t& acc, bool first,
+                                          uint32_t dec) {
+  if (first) {
+    acc = dec;
+  } else {
+    acc = f2raw<T>(raw2f<T>(acc) + raw2f<T>(dec));
+  }
+}
+
+// Slice owning work unit b: largest i with cum[i] <= b.
+__device__ __forceinline__ int find_slice(const int64_t* __restrict__ cum,
+                                          int nslices, int64_t b) {
+  int lo = 0, hi = nslices;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (cum[mid] <= b) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+template <typename T>
+__device__ __forceinline__ SliceGeom geom_of(int64_t n, int32_t bucket,
+                                             int32_t flags, int bits) {
+  return slice_geom(n, bucket, bits, sizeof(T),
+                    (flags & kFlagSkipIncomplete) != 0);
 }
 
 // Packed-pair min/max for 16-bit dtypes (v_pk_min/max_f16|bf16): phase A of
@@ -259,31 +375,6 @@ __device__ __forceinline__ void store8(T* p, bool aligned16,
   R* q = reinterpret_cast<R*>(p);
 #pragma unroll
   for (int j = 0; j < 8; j++) q[j] = static_cast<R>(r[j]);
-}
-
-__device__ __forceinline__ void load4f(const float* p, bool aligned16,
-                                       uint32_t (&r)[4]) {
-  if (aligned16) {
-    const int4 a = *reinterpret_cast<const int4*>(p);
-    r[0] = a.x; r[1] = a.y; r[2] = a.z; r[3] = a.w;
-    return;
-  }
-  const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-#pragma unroll
-  for (int j = 0; j < 4; j++) r[j] = q[j];
-}
-
-__device__ __forceinline__ void store4f(float* p, bool aligned16,
-                                        const uint32_t (&r)[4]) {
-  if (aligned16) {
-    const int4 a = {static_cast<int>(r[0]), static_cast<int>(r[1]),
-                    static_cast<int>(r[2]), static_cast<int>(r[3])};
-    *reinterpret_cast<int4*>(p) = a;
-    return;
-  }
-  uint32_t* q = reinterpret_cast<uint32_t*>(p);
-#pragma unroll
-  for (int j = 0; j < 4; j++) q[j] = r[j];
 }
 
 // Write the low `nb` bytes of v to p (little-endian), widest aligned stores.
@@ -432,28 +523,18 @@ struct QuantRun {
     const bool live = unitf >= kEps;
     const float rinv = live ? 1.0f / unitf : 0.0f;
     const int64_t gbase = lb * (int64_t)ngroups;
-    using acc_t =
-        typename std::conditional<(BITS <= 4), uint32_t, uint64_t>::type;
 #pragma unroll
     for (int k = 0; k < G; k++) {
       const int g = lane + k * kWave;
       if (g >= ngroups) continue;
-      acc_t value = 0;
+      pack_acc_t<BITS> value = 0;
       if (live) {
-        const uint64_t pr =
-            stochastic
-                ? rand_pack(seed, (static_cast<uint64_t>(slice_idx) << 44) |
-                                      static_cast<uint64_t>(gbase + g))
-                : 0;
+        uint32_t r[8];
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-          const float rnd = stochastic ? rand_lane(pr, j) : 0.5f;
-          const float dd = (raw2f<T>(elem(s, k, j)) - minf) * rinv + rnd;
-          const uint32_t level =
-              static_cast<uint32_t>(fminf(floorf(dd), divisor));
-          value |=
-              static_cast<acc_t>(level & ((1u << BITS) - 1)) << (j * BITS);
-        }
+        for (int j = 0; j < 8; j++) r[j] = elem(s, k, j);
+        value = encode_pack<T, BITS>(
+            r, minf, rinv, divisor,
+            pack_rand(seed, stochastic, slice_idx, gbase + g), stochastic);
       }
       store_bytes(packed + (gbase + g) * BITS, static_cast<uint64_t>(value),
                   BITS);
@@ -564,24 +645,19 @@ struct QuantSub {
         meta[2 * lb + 1] = static_cast<R>(f2raw<T>(lmin));
       }
       const int64_t g = lb * L + li;  // global group index in the slice
-      using acc_t =
-          typename std::conditional<(BITS <= 4), uint32_t, uint64_t>::type;
-      acc_t value = 0;
+      pack_acc_t<BITS> value = 0;
       if (unitf >= kEps) {
+        // encode_pack's loop written out from the same primitives: going
+        // through the helper shifts the 16-bit instantiations' register
+        // allocation (107 -> 102 VGPR), and this kernel is kept at the
+        // allocation it was measured with
         const float rinv = 1.0f / unitf;
-        const uint64_t pr =
-            stochastic
-                ? rand_pack(seed, (static_cast<uint64_t>(slice_idx) << 44) |
-                                      static_cast<uint64_t>(g))
-                : 0;
+        const uint64_t pr = pack_rand(seed, stochastic, slice_idx, g);
 #pragma unroll
         for (int j = 0; j < 8; j++) {
           const float rnd = stochastic ? rand_lane(pr, j) : 0.5f;
-          const float dd = (raw2f<T>(r[j]) - minf) * rinv + rnd;
-          const uint32_t level =
-              static_cast<uint32_t>(fminf(floorf(dd), divisor));
-          value |=
-              static_cast<acc_t>(level & ((1u << BITS) - 1)) << (j * BITS);
+          value |= level_bits<BITS, pack_acc_t<BITS>>(
+              quant_level<T>(r[j], minf, rinv, rnd, divisor), j);
         }
       }
       store_bytes(packed + g * BITS, static_cast<uint64_t>(value), BITS);
@@ -589,7 +665,7 @@ struct QuantSub {
   }
 };
 
-// Lean fast-path kernel (see compress.h launch_quantize_fast): only the
+// Lean fast-path kernel (see compress.h LaunchKind kFast): only the
 // QuantRun register path is instantiated, so the register allocator is not
 // forced to the generic/EF paths' footprint (k_quantize<float,4,true>
 // allocates 139 VGPRs = 3 waves/SIMD; this kernel ~half that).
@@ -605,16 +681,10 @@ __global__ __launch_bounds__(kThreads) void k_quantize_fast(
   constexpr float divisor = static_cast<float>((1 << BITS) - 1);
   int64_t b = wid;
   while (b < total_buckets) {
-    int lo = 0, hi = nslices;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (cum[mid] <= b) lo = mid; else hi = mid;
-    }
+    const int lo = find_slice(cum, nslices, b);
     const QuantDesc d = descs[lo];
-    const bool skip = (d.flags & kFlagSkipIncomplete) != 0;
-    const int64_t nb_slice =
-        skip ? d.n / d.bucket
-             : (d.n + d.bucket - 1) / static_cast<int64_t>(d.bucket);
+    const int64_t meta_bytes =
+        geom_of<T>(d.n, d.bucket, d.flags, BITS).meta_bytes;
     const int64_t nb_full = cum[lo + 1] - cum[lo];
     const int64_t lb = b - cum[lo];
     const int ngroups = d.bucket >> 3;
@@ -623,8 +693,7 @@ __global__ __launch_bounds__(kThreads) void k_quantize_fast(
   do {                                                                     \
     QuantRun<T, BITS, GV> qr{reinterpret_cast<const T*>(d.in),             \
                              reinterpret_cast<R*>(d.out),                  \
-                             reinterpret_cast<uint8_t*>(d.out) +           \
-                                 2 * sizeof(R) * nb_slice,                 \
+                             d.out + meta_bytes,                           \
                              lane,    ngroups, divisor,                    \
                              seed,    stochastic, lo};                     \
     qr.run(lb, count, nw);                                                 \
@@ -664,16 +733,10 @@ __global__ __launch_bounds__(kThreads) void k_quantize_sub(
   constexpr float divisor = static_cast<float>((1 << BITS) - 1);
   int64_t b = wid;
   while (b < total_buckets) {
-    int lo = 0, hi = nslices;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (cum[mid] <= b) lo = mid; else hi = mid;
-    }
+    const int lo = find_slice(cum, nslices, b);
     const QuantDesc d = descs[lo];
-    const bool skip = (d.flags & kFlagSkipIncomplete) != 0;
-    const int64_t nb_slice =
-        skip ? d.n / d.bucket
-             : (d.n + d.bucket - 1) / static_cast<int64_t>(d.bucket);
+    const int64_t meta_bytes =
+        geom_of<T>(d.n, d.bucket, d.flags, BITS).meta_bytes;
     const int64_t nb_full = cum[lo + 1] - cum[lo];
     const int64_t lb = b - cum[lo];
     const int ngroups = d.bucket >> 3;
@@ -682,8 +745,7 @@ __global__ __launch_bounds__(kThreads) void k_quantize_sub(
   do {                                                                     \
     QuantSub<T, BITS, LV> q{reinterpret_cast<const T*>(d.in),              \
                             reinterpret_cast<R*>(d.out),                   \
-                            reinterpret_cast<uint8_t*>(d.out) +            \
-                                2 * sizeof(R) * nb_slice,                  \
+                            d.out + meta_bytes,                            \
                             lane, divisor, seed, stochastic, lo};          \
     q.run(lb, count, nw);                                                  \
   } while (0)
@@ -718,23 +780,14 @@ __global__ __launch_bounds__(kThreads) void k_quantize(
   constexpr int MAXG = 4;  // register-stashed packs per lane (bucket <= 2048)
 
   for (int64_t b = wid; b < total_buckets; b += nw) {
-    int lo = 0, hi = nslices;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (cum[mid] <= b) lo = mid; else hi = mid;
-    }
+    const int lo = find_slice(cum, nslices, b);
     const QuantDesc d = descs[lo];
-    const bool skip = (d.flags & kFlagSkipIncomplete) != 0;
-    const int64_t nq =
-        skip ? (d.n / d.bucket) * static_cast<int64_t>(d.bucket) : d.n;
-    int64_t nb_slice = cum[lo + 1] - cum[lo];
-    int64_t lb = b - cum[lo];
-    if (d.flags & kFlagTailOnly) {
-      // full buckets were handled by k_quantize_fast; this desc's single
-      // cum entry maps to the trailing partial bucket
-      lb += d.n / d.bucket;
-      nb_slice = (d.n + d.bucket - 1) / static_cast<int64_t>(d.bucket);
-    }
+    const SliceGeom sg = geom_of<T>(d.n, d.bucket, d.flags, BITS);
+    const int64_t nq = sg.nq;
+    // kFlagTailOnly: the full buckets were handled by the fast/sub kernel;
+    // this desc's single cum entry maps to the trailing partial bucket
+    const int64_t lb =
+        b - cum[lo] + ((d.flags & kFlagTailOnly) ? d.n / d.bucket : 0);
     const int64_t bstart = lb * static_cast<int64_t>(d.bucket);
     const int cur = static_cast<int>(min(static_cast<int64_t>(d.bucket), nq - bstart));
     const T* in = reinterpret_cast<const T*>(d.in) + bstart;
@@ -743,44 +796,9 @@ __global__ __launch_bounds__(kThreads) void k_quantize(
 
     uint32_t stash[MAXG][8];
     float lmin = INFINITY, lmax = -INFINITY;
-    // fast path: full bucket, whole groups per lane (wave-uniform branch)
     const bool full = cur == d.bucket && (cur & 7) == 0 && al16;
     T* const fbp = d.fb ? reinterpret_cast<T*>(d.fb) + bstart : nullptr;
-    if (full && ngroups <= MAXG * kWave && !fbp) {
-      if constexpr (sizeof(T) == 2) {
-        using PK = Pk2<T>;
-        typename PK::P pmin = bitcast<typename PK::P>(PK::kInf);
-        typename PK::P pmax = bitcast<typename PK::P>(PK::kNInf);
-        for (int g = lane, gi = 0; g < ngroups; g += kWave, gi++) {
-          const int4 a = *reinterpret_cast<const int4*>(in + g * 8);
-          const uint32_t w[4] = {static_cast<uint32_t>(a.x),
-                                 static_cast<uint32_t>(a.y),
-                                 static_cast<uint32_t>(a.z),
-                                 static_cast<uint32_t>(a.w)};
-#pragma unroll
-          for (int k = 0; k < 4; k++) {
-            const auto v = bitcast<typename PK::P>(w[k]);
-            pmin = PK::min(pmin, v);
-            pmax = PK::max(pmax, v);
-          }
-#pragma unroll
-          for (int j = 0; j < 8; j++)
-            stash[gi][j] = (w[j >> 1] >> ((j & 1) * 16)) & 0xFFFF;
-        }
-        lmin = fminf(PK::lo(pmin), PK::hi(pmin));
-        lmax = fmaxf(PK::lo(pmax), PK::hi(pmax));
-      } else {
-        for (int g = lane, gi = 0; g < ngroups; g += kWave, gi++) {
-          load8<T>(in + g * 8, true, stash[gi]);
-#pragma unroll
-          for (int j = 0; j < 8; j++) {
-            const float f = raw2f<T>(stash[gi][j]);
-            lmin = fminf(lmin, f);
-            lmax = fmaxf(lmax, f);
-          }
-        }
-      }
-    } else if (full && ngroups <= MAXG * kWave && fbp) {
+    if (full && ngroups <= MAXG * kWave && fbp) {
       // error-feedback: stash the T-rounded x+fb and reduce over it.
       // fb alignment is independent of the input's (the engine rebases the
       // phase-2 feedback base by a partition offset), so probe it separately.
@@ -836,37 +854,10 @@ __global__ __launch_bounds__(kThreads) void k_quantize(
     }
 
     if constexpr (ENCODE) {
-      uint8_t* packed =
-          reinterpret_cast<uint8_t*>(d.out) + 2 * sizeof(R) * nb_slice;
-      const int64_t num_char = (nq * BITS + 7) >> 3;
+      uint8_t* packed = d.out + sg.meta_bytes;
       const int64_t gbase = bstart >> 3;
       const bool live = unitf >= kEps;
       const float rinv = 1.0f / unitf;  // hoisted: fp32 div is 1/4 VALU rate
-      if (full && ngroups <= MAXG * kWave && live && !fbp) {
-        // 8 levels fit a uint32 when BITS <= 4: halves the shift/or cost
-        using acc_t =
-            typename std::conditional<(BITS <= 4), uint32_t, uint64_t>::type;
-        for (int g = lane, gi = 0; g < ngroups; g += kWave, gi++) {
-          const uint64_t pr =
-              stochastic
-                  ? rand_pack(seed, (static_cast<uint64_t>(lo) << 44) |
-                                        static_cast<uint64_t>(gbase + g))
-                  : 0;
-          acc_t value = 0;
-#pragma unroll
-          for (int j = 0; j < 8; j++) {
-            const float rnd = stochastic ? rand_lane(pr, j) : 0.5f;
-            const float dd = (raw2f<T>(stash[gi][j]) - minf) * rinv + rnd;
-            const uint32_t level =
-                static_cast<uint32_t>(fminf(floorf(dd), divisor));
-            value |= static_cast<acc_t>(level & ((1u << BITS) - 1))
-                     << (j * BITS);
-          }
-          store_bytes(packed + (gbase + g) * BITS,
-                      static_cast<uint64_t>(value), BITS);
-        }
-        continue;
-      }
       for (int g = lane, gi = 0; g < ngroups; g += kWave, gi++) {
         uint32_t r[8];
         const int m = min(8, cur - g * 8);
@@ -887,34 +878,23 @@ __global__ __launch_bounds__(kThreads) void k_quantize(
         uint64_t value = 0;
         uint32_t lv[8] = {};
         if (live) {
-          const uint64_t pr =
-              stochastic ? rand_pack(seed, (static_cast<uint64_t>(lo) << 44) |
-                                               static_cast<uint64_t>(gbase + g))
-                         : 0;
-          for (int j = 0; j < m; j++) {
-            const float rnd = stochastic ? rand_lane(pr, j) : 0.5f;
-            const float dd = (raw2f<T>(r[j]) - minf) * rinv + rnd;
-            const uint32_t level =
-                static_cast<uint32_t>(fminf(floorf(dd), divisor));
-            lv[j] = level;
-            value |= static_cast<uint64_t>(level & ((1u << BITS) - 1))
-                     << (j * BITS);
-          }
+          value = encode_pack<T, BITS>(
+              r, m, minf, rinv, divisor,
+              pack_rand(seed, stochastic, lo, gbase + g), stochastic, lv);
         }
         if (fbp) {
           // residual: (x+fb) - decode(level), rounded to T per the spec
           R* f = reinterpret_cast<R*>(fbp) + g * 8;
           for (int j = 0; j < m; j++) {
-            const uint32_t prod =
-                f2raw<T>(unitf * static_cast<float>(live ? lv[j] : 0));
-            const uint32_t dec = f2raw<T>(minf + raw2f<T>(prod));
+            const uint32_t dec =
+                decode_raw<T>(unit_raw, f2raw<T>(minf), lv[j]);
             f[j] = static_cast<R>(
                 f2raw<T>(raw2f<T>(r[j]) - raw2f<T>(dec)));
           }
         }
         const int64_t gb = (gbase + g) * BITS;
-        const int nbytes =
-            static_cast<int>(min(static_cast<int64_t>(BITS), num_char - gb));
+        const int nbytes = static_cast<int>(
+            min(static_cast<int64_t>(BITS), sg.packed_bytes - gb));
         store_bytes(packed + gb, value, nbytes);
       }
     }
@@ -934,25 +914,17 @@ __global__ __launch_bounds__(kThreads) void k_pack_generic(
   constexpr float divisor = static_cast<float>((1 << BITS) - 1);
   for (int s = 0; s < nslices; s++) {
     const QuantDesc d = descs[s];
-    const bool skip = (d.flags & kFlagSkipIncomplete) != 0;
-    const int64_t nq =
-        skip ? (d.n / d.bucket) * static_cast<int64_t>(d.bucket) : d.n;
+    const SliceGeom sg = geom_of<T>(d.n, d.bucket, d.flags, BITS);
+    const int64_t nq = sg.nq;
     const int64_t ngroups = (nq + 7) >> 3;
-    const int64_t nb_slice =
-        skip ? d.n / d.bucket : (d.n + d.bucket - 1) / d.bucket;
     const R* meta = reinterpret_cast<const R*>(d.out);
-    uint8_t* packed =
-        reinterpret_cast<uint8_t*>(d.out) + 2 * sizeof(R) * nb_slice;
-    const int64_t num_char = (nq * BITS + 7) >> 3;
+    uint8_t* packed = d.out + sg.meta_bytes;
     const R* in = reinterpret_cast<const R*>(d.in);
     const bool small = d.n < (int64_t(1) << 31);
     for (int64_t g = t0; g < ngroups; g += stride) {
       const int m = static_cast<int>(min(static_cast<int64_t>(8), nq - g * 8));
       uint64_t value = 0;
-      const uint64_t pr =
-          stochastic ? rand_pack(seed, (static_cast<uint64_t>(s) << 44) |
-                                           static_cast<uint64_t>(g))
-                     : 0;
+      const uint64_t pr = pack_rand(seed, stochastic, s, g);
       for (int j = 0; j < m; j++) {
         const int64_t eidx = g * 8 + j;
         const int64_t bk =
@@ -962,15 +934,13 @@ __global__ __launch_bounds__(kThreads) void k_pack_generic(
         const float unitf = raw2f<T>(meta[2 * bk]);
         if (unitf < kEps) continue;
         const float minf = raw2f<T>(meta[2 * bk + 1]);
-        const float rinv = 1.0f / unitf;
         const float rnd = stochastic ? rand_lane(pr, j) : 0.5f;
-        const float dd = (raw2f<T>(in[eidx]) - minf) * rinv + rnd;
-        const uint32_t level = static_cast<uint32_t>(fminf(floorf(dd), divisor));
-        value |= static_cast<uint64_t>(level & ((1u << BITS) - 1)) << (j * BITS);
+        value |= level_bits<BITS, uint64_t>(
+            quant_level<T>(in[eidx], minf, 1.0f / unitf, rnd, divisor), j);
       }
       const int64_t gb = g * BITS;
-      const int nbytes =
-          static_cast<int>(min(static_cast<int64_t>(BITS), num_char - gb));
+      const int nbytes = static_cast<int>(
+          min(static_cast<int64_t>(BITS), sg.packed_bytes - gb));
       store_bytes(packed + gb, value, nbytes);
     }
   }
@@ -1062,6 +1032,17 @@ __device__ __forceinline__ void store16B(void* p, const uint32_t (&r)[4]) {
   }
 }
 
+// Runtime-alignment forms, for the generic kernel only.
+__device__ __forceinline__ void load16B(const void* p, bool al16,
+                                        uint32_t (&r)[4]) {
+  if (al16) load16B<true>(p, r); else load16B<false>(p, r);
+}
+
+__device__ __forceinline__ void store16B(void* p, bool al16,
+                                         const uint32_t (&r)[4]) {
+  if (al16) store16B<true>(p, r); else store16B<false>(p, r);
+}
+
 // Incremental bucket-index tracker: replaces the per-iteration integer
 // division (a ~40-instruction software sequence that dominated the round-1
 // hot loop) with one uniform quotient add + carry per iteration.  Valid
@@ -1127,18 +1108,11 @@ __device__ void deq_f32_fast(const DequantDesc& d,
       }
 #pragma unroll
       for (int u = 0; u < U; u++) {
-        const float unitf = bitcast<float>(ur[u]);
-        const float minf = bitcast<float>(mr[u]);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-          const uint32_t lvl = static_cast<uint32_t>(
-              (value[u] >> (j * BITS)) & ((1u << BITS) - 1));
-          const float dec = minf + unitf * static_cast<float>(lvl);
-          if (!HAVE && sidx == 0) {
-            v[u][j] = bitcast<uint32_t>(dec);
-          } else {
-            v[u][j] = bitcast<uint32_t>(bitcast<float>(v[u][j]) + dec);
-          }
+          accum_raw<float>(
+              v[u][j], !HAVE && sidx == 0,
+              decode_raw<float>(ur[u], mr[u], pack_level<BITS>(value[u], j)));
         }
       }
     }
@@ -1162,18 +1136,11 @@ __device__ void deq_f32_fast(const DequantDesc& d,
           load_pack_half<BITS>(src, w >> 1, static_cast<int>(w & 1));
       uint32_t ur, mr;
       load_meta_pair<uint32_t>(meta, bkw, ur, mr);
-      const float unitf = bitcast<float>(ur);
-      const float minf = bitcast<float>(mr);
 #pragma unroll
       for (int j = 0; j < 4; j++) {
-        const uint32_t lvl = static_cast<uint32_t>((value >> (j * BITS)) &
-                                                   ((1u << BITS) - 1));
-        const float dec = minf + unitf * static_cast<float>(lvl);
-        if (!HAVE && sidx == 0) {
-          v[j] = bitcast<uint32_t>(dec);
-        } else {
-          v[j] = bitcast<uint32_t>(bitcast<float>(v[j]) + dec);
-        }
+        accum_raw<float>(
+            v[j], !HAVE && sidx == 0,
+            decode_raw<float>(ur, mr, pack_level<BITS>(value, j)));
       }
     }
     store16B<AL16>(outp, v);
@@ -1212,19 +1179,10 @@ __device__ void deq_16_fast(const DequantDesc& d,
       const uint64_t value = load_pack_full<BITS>(src, g);
       uint32_t ur, mr;
       load_meta_pair<R>(meta, bk.bk, ur, mr);
-      const float unitf = raw2f<T>(ur);
-      const float minf = raw2f<T>(mr);
 #pragma unroll
       for (int j = 0; j < 8; j++) {
-        const uint32_t lvl = static_cast<uint32_t>((value >> (j * BITS)) &
-                                                   ((1u << BITS) - 1));
-        const uint32_t prod = f2raw<T>(unitf * static_cast<float>(lvl));
-        const uint32_t dec = f2raw<T>(minf + raw2f<T>(prod));
-        if (!HAVE && sidx == 0) {
-          v[j] = dec;
-        } else {
-          v[j] = f2raw<T>(raw2f<T>(v[j]) + raw2f<T>(dec));
-        }
+        accum_raw<T>(v[j], !HAVE && sidx == 0,
+                     decode_raw<T>(ur, mr, pack_level<BITS>(value, j)));
       }
     }
     if constexpr (AL16) {
@@ -1253,6 +1211,10 @@ __global__ __launch_bounds__(kThreads) void k_dequant_fast(
   const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   for (int si = 0; si < nslices; si++) {
     const DequantDesc d = descs[si];
+    // slice_geom's nq / meta_bytes written out: through the helper the
+    // per-slice scalar prologue compiles differently (11 instructions
+    // shorter, other SGPR numbering through the whole kernel), and this
+    // kernel is kept instruction-identical to the code it was measured with
     const bool skip = (d.flags & kFlagSkipIncomplete) != 0;
     const int64_t nq =
         skip ? (d.n / d.bucket) * static_cast<int64_t>(d.bucket) : d.n;
@@ -1310,26 +1272,20 @@ __global__ __launch_bounds__(kThreads) void k_dequant_fast(
 // ---------------------------------------------------------------------------
 template <typename T, int BITS>
 __global__ __launch_bounds__(kThreads) void k_dequant(
-    const DequantDesc* __restrict__ descs, const int64_t* __restrict__ cum,
-    int nslices, int64_t total_groups) {
+    const DequantDesc* __restrict__ descs, int nslices) {
   // Outer loop over slices with every per-slice quantity hoisted; the inner
   // grid-stride loop over FULL groups is branch-free (no tail/alignment
   // checks, no exec-mask divergence) -- the original per-group binary-search
   // form spent >80% of its instructions on repeated int64 address math.
   using R = typename RawOf<T>::type;
-  (void)cum;
-  (void)total_groups;
   const int64_t t0 =
       static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   for (int si = 0; si < nslices; si++) {
     const DequantDesc d = descs[si];
-    const bool skip = (d.flags & kFlagSkipIncomplete) != 0;
-    const int64_t nq =
-        skip ? (d.n / d.bucket) * static_cast<int64_t>(d.bucket) : d.n;
-    const int64_t nb_slice =
-        skip ? d.n / d.bucket : (d.n + d.bucket - 1) / d.bucket;
-    const int64_t meta_bytes = 2 * sizeof(R) * nb_slice;
+    const SliceGeom sg = geom_of<T>(d.n, d.bucket, d.flags, BITS);
+    const int64_t nq = sg.nq;
+    const int64_t meta_bytes = sg.meta_bytes;
     const int64_t full_groups = nq >> 3;
     const bool oneb = (d.bucket & 7) == 0;
     const uint32_t B8 = oneb ? static_cast<uint32_t>(d.bucket >> 3) : 1u;
@@ -1362,7 +1318,7 @@ __global__ __launch_bounds__(kThreads) void k_dequant(
         for (int u = 0; u < U; u++) {
           ws2[u] = w + u * stride;
           outp[u] = reinterpret_cast<float*>(d.out) + ws2[u] * 4;
-          if (have) load4f(outp[u], al16, v[u]);
+          if (have) load16B(outp[u], al16, v[u]);
           bk0[u] = oneb
                        ? (small ? static_cast<uint32_t>(ws2[u]) / B4
                                 : static_cast<uint32_t>(
@@ -1392,22 +1348,14 @@ __global__ __launch_bounds__(kThreads) void k_dequant(
 #pragma unroll
             for (int j = 0; j < 4; j++) {
               const int64_t bk = oneb ? bk0[u] : (ws2[u] * 4 + j) / d.bucket;
-              const uint32_t lvl = static_cast<uint32_t>(
-                  (value[u] >> (j * BITS)) & ((1u << BITS) - 1));
-              const uint32_t prod =
-                  f2raw<T>(raw2f<T>(meta[2 * bk]) * static_cast<float>(lvl));
-              const uint32_t dec =
-                  f2raw<T>(raw2f<T>(meta[2 * bk + 1]) + raw2f<T>(prod));
-              if (!have && sidx == 0) {
-                v[u][j] = dec;
-              } else {
-                v[u][j] = f2raw<T>(raw2f<T>(v[u][j]) + raw2f<T>(dec));
-              }
+              accum_raw<T>(v[u][j], !have && sidx == 0,
+                           decode_raw<T>(meta[2 * bk], meta[2 * bk + 1],
+                                         pack_level<BITS>(value[u], j)));
             }
           }
         }
 #pragma unroll
-        for (int u = 0; u < U; u++) store4f(outp[u], al16, v[u]);
+        for (int u = 0; u < U; u++) store16B(outp[u], al16, v[u]);
       }
       for (; w < full_subs; w += stride) {
         const int64_t g = w >> 1;
@@ -1415,7 +1363,7 @@ __global__ __launch_bounds__(kThreads) void k_dequant(
         uint32_t v[4];
         bool have = d.add != 0;
         float* outp = reinterpret_cast<float*>(d.out) + w * 4;
-        if (have) load4f(outp, al16, v);
+        if (have) load16B(outp, al16, v);
         const uint32_t bk0 =
             oneb ? (small ? static_cast<uint32_t>(w) / B4
                           : static_cast<uint32_t>(
@@ -1439,19 +1387,11 @@ __global__ __launch_bounds__(kThreads) void k_dequant(
               const int64_t bk = (w * 4 + j) / d.bucket;
               load_meta_pair<R>(meta, bk, ur, mr);
             }
-            const uint32_t lvl = static_cast<uint32_t>(
-                (value >> (j * BITS)) & ((1u << BITS) - 1));
-            const uint32_t prod =
-                f2raw<T>(raw2f<T>(ur) * static_cast<float>(lvl));
-            const uint32_t dec = f2raw<T>(raw2f<T>(mr) + raw2f<T>(prod));
-            if (!have && sidx == 0) {
-              v[j] = dec;
-            } else {
-              v[j] = f2raw<T>(raw2f<T>(v[j]) + raw2f<T>(dec));
-            }
+            accum_raw<T>(v[j], !have && sidx == 0,
+                         decode_raw<T>(ur, mr, pack_level<BITS>(value, j)));
           }
         }
-        store4f(outp, al16, v);
+        store16B(outp, al16, v);
       }
       }  // generic fp32 path
     f32_tail:
@@ -1461,29 +1401,19 @@ __global__ __launch_bounds__(kThreads) void k_dequant(
         for (int64_t eidx = full_subs * 4; eidx < nq; eidx++) {
           const int64_t g = eidx >> 3;
           const int j = static_cast<int>(eidx & 7);
-          const int64_t num_char = (nq * BITS + 7) >> 3;
           const int nbytes = static_cast<int>(
-              min(static_cast<int64_t>(BITS), num_char - g * BITS));
+              min(static_cast<int64_t>(BITS), sg.packed_bytes - g * BITS));
           const int64_t bk = eidx / d.bucket;
-          bool first = true;
+          uint32_t v = d.add ? outr[eidx] : 0;
           for (int sidx = 0; sidx < d.nsrc; sidx++) {
             const uint8_t* src = in0 + sidx * d.src_stride;
             const R* meta = reinterpret_cast<const R*>(src - meta_bytes);
             const uint64_t value = load_bytes(src + g * BITS, nbytes);
-            const uint32_t lvl = static_cast<uint32_t>(
-                (value >> (j * BITS)) & ((1u << BITS) - 1));
-            const uint32_t prod = f2raw<T>(raw2f<T>(meta[2 * bk]) *
-                                           static_cast<float>(lvl));
-            const uint32_t dec =
-                f2raw<T>(raw2f<T>(meta[2 * bk + 1]) + raw2f<T>(prod));
-            if (first && !d.add) {
-              outr[eidx] = static_cast<R>(dec);
-            } else {
-              outr[eidx] = static_cast<R>(
-                  f2raw<T>(raw2f<T>(outr[eidx]) + raw2f<T>(dec)));
-            }
-            first = false;
+            accum_raw<T>(v, sidx == 0 && !d.add,
+                         decode_raw<T>(meta[2 * bk], meta[2 * bk + 1],
+                                       pack_level<BITS>(value, j)));
           }
+          outr[eidx] = static_cast<R>(v);
         }
       }
       continue;  // next slice (16-bit loop below is for 2-byte dtypes)
@@ -1512,15 +1442,8 @@ __global__ __launch_bounds__(kThreads) void k_dequant(
             const int64_t bk = (g * 8 + j) / d.bucket;
             load_meta_pair<R>(meta, bk, ur, mr);
           }
-          const uint32_t lvl = static_cast<uint32_t>((value >> (j * BITS)) &
-                                                     ((1u << BITS) - 1));
-          const uint32_t prod = f2raw<T>(raw2f<T>(ur) * static_cast<float>(lvl));
-          const uint32_t dec = f2raw<T>(raw2f<T>(mr) + raw2f<T>(prod));
-          if (!have && sidx == 0) {
-            v[j] = dec;
-          } else {
-            v[j] = f2raw<T>(raw2f<T>(v[j]) + raw2f<T>(dec));
-          }
+          accum_raw<T>(v[j], !have && sidx == 0,
+                       decode_raw<T>(ur, mr, pack_level<BITS>(value, j)));
         }
       }
       store8<T>(outp, al16, v);
@@ -1531,9 +1454,8 @@ __global__ __launch_bounds__(kThreads) void k_dequant(
     const int mtail = static_cast<int>(nq - full_groups * 8);
     if (mtail > 0 && t0 == 0) {
       const int64_t g = full_groups;
-      const int64_t num_char = (nq * BITS + 7) >> 3;
       const int nbytes = static_cast<int>(
-          min(static_cast<int64_t>(BITS), num_char - g * BITS));
+          min(static_cast<int64_t>(BITS), sg.packed_bytes - g * BITS));
       R* outp = reinterpret_cast<R*>(d.out) + g * 8;
       for (int sidx = 0; sidx < d.nsrc; sidx++) {
         const uint8_t* src = in0 + sidx * d.src_stride;
@@ -1541,18 +1463,12 @@ __global__ __launch_bounds__(kThreads) void k_dequant(
         const uint64_t value = load_bytes(src + g * BITS, nbytes);
         for (int j = 0; j < mtail; j++) {
           const int64_t bk = (g * 8 + j) / d.bucket;
-          const uint32_t lvl = static_cast<uint32_t>((value >> (j * BITS)) &
-                                                     ((1u << BITS) - 1));
-          const float unitf = raw2f<T>(meta[2 * bk]);
-          const float minf = raw2f<T>(meta[2 * bk + 1]);
-          const uint32_t prod = f2raw<T>(unitf * static_cast<float>(lvl));
-          const uint32_t dec = f2raw<T>(minf + raw2f<T>(prod));
-          if (sidx == 0 && !d.add) {
-            outp[j] = static_cast<R>(dec);
-          } else {
-            outp[j] = static_cast<R>(
-                f2raw<T>(raw2f<T>(outp[j]) + raw2f<T>(dec)));
-          }
+          const bool first = sidx == 0 && !d.add;
+          uint32_t v = first ? 0 : outp[j];
+          accum_raw<T>(v, first,
+                       decode_raw<T>(meta[2 * bk], meta[2 * bk + 1],
+                                     pack_level<BITS>(value, j)));
+          outp[j] = static_cast<R>(v);
         }
       }
     }
@@ -1572,13 +1488,12 @@ __global__ __launch_bounds__(kThreads) void k_residual_q(
   for (int s = 0; s < nslices; s++) {
     const QuantDesc d = descs[s];
     if (!(d.flags & kFlagSkipIncomplete)) continue;
-    const int64_t nb = d.n / d.bucket;
-    const int64_t nq = nb * static_cast<int64_t>(d.bucket);
-    const int64_t r = d.n - nq;
+    const SliceGeom sg = geom_of<T>(d.n, d.bucket, d.flags, bits);
+    const int64_t nq = sg.nq;
+    const int64_t r = sg.resid;
     if (r == 0) continue;
     const R* src = reinterpret_cast<const R*>(d.in) + nq;
-    R* dst = reinterpret_cast<R*>(
-        d.out + 2 * sizeof(R) * nb + ((nq * bits + 7) / 8 + 7) / 8 * 8);
+    R* dst = reinterpret_cast<R*>(d.out + sg.resid_off);
     if (d.fb) {
       // error feedback: the raw residual tail carries x+fb exactly, so the
       // new residual is zero
@@ -1604,26 +1519,17 @@ __global__ __launch_bounds__(kThreads) void k_residual_d(
   for (int s = 0; s < nslices; s++) {
     const DequantDesc d = descs[s];
     if (!(d.flags & kFlagSkipIncomplete)) continue;
-    const int64_t nb = d.n / d.bucket;
-    const int64_t nq = nb * static_cast<int64_t>(d.bucket);
-    const int64_t r = d.n - nq;
+    const SliceGeom sg = geom_of<T>(d.n, d.bucket, d.flags, bits);
+    const int64_t r = sg.resid;
     if (r == 0) continue;
-    const int64_t comp = 2 * sizeof(R) * nb + ((nq * bits + 7) / 8 + 7) / 8 * 8;
-    R* outp = reinterpret_cast<R*>(d.out) + nq;
+    R* outp = reinterpret_cast<R*>(d.out) + sg.nq;
     for (int64_t i = t0; i < r; i += stride) {
-      uint32_t v;
-      bool have = d.add != 0;
-      if (have) v = outp[i];
+      uint32_t v = 0;
+      if (d.add) v = outp[i];
       for (int src = 0; src < d.nsrc; src++) {
         const R* rp = reinterpret_cast<const R*>(d.in + src * d.src_stride +
-                                                 comp);
-        const uint32_t dec = rp[i];
-        if (!have && src == 0) {
-          v = dec;
-          have = true;
-        } else {
-          v = f2raw<T>(raw2f<T>(v) + raw2f<T>(dec));
-        }
+                                                 sg.resid_off);
+        accum_raw<T>(v, !d.add && src == 0, rp[i]);
       }
       outp[i] = static_cast<R>(v);
     }
@@ -1686,114 +1592,60 @@ inline int grid_for(int64_t work, int per_block) {
 
 }  // namespace
 
-void launch_quantize_batch(const QuantDesc* descs, const int64_t* cum,
-                           int nslices, int64_t total_buckets, DType dt,
-                           int bits, uint64_t seed, bool stochastic,
-                           hipStream_t stream, bool buckets_mult8,
-                           bool any_residual) {
+void launch(const QuantGroup& g, const QuantDesc* descs, const int64_t* cum,
+            DType dt, uint64_t seed, bool stochastic, hipStream_t stream) {
+  const int nslices = static_cast<int>(g.descs.size());
   if (nslices <= 0) return;
-  const int grid = grid_for(std::max<int64_t>(total_buckets, 1),
-                            kThreads / kWave);
-  CGX_DISPATCH_T(dt, CGX_DISPATCH_BITS(bits, {
+  const int64_t total_buckets = g.cum.back();
+  const dim3 grid(grid_for(std::max<int64_t>(total_buckets, 1),
+                           kThreads / kWave));
+  const dim3 block(kThreads);
+  const int stoch = stochastic;
+#define CGX_QUANT(...)                                                   \
+  hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, stream, descs, cum,  \
+                     nslices, total_buckets, seed, stoch)
+  CGX_DISPATCH_T(dt, CGX_DISPATCH_BITS(g.bits, {
     if (total_buckets > 0) {
-      if (buckets_mult8) {
-        hipLaunchKernelGGL((k_quantize<T, BITS, true>), dim3(grid),
-                           dim3(kThreads), 0, stream, descs, cum, nslices,
-                           total_buckets, seed, (int)stochastic);
-      } else {
-        hipLaunchKernelGGL((k_quantize<T, BITS, false>), dim3(grid),
-                           dim3(kThreads), 0, stream, descs, cum, nslices,
-                           total_buckets, seed, (int)stochastic);
-        hipLaunchKernelGGL((k_pack_generic<T, BITS>), dim3(grid),
-                           dim3(kThreads), 0, stream, descs, nslices, seed,
-                           (int)stochastic);
+      switch (g.kind) {
+        case kFast:
+          if (g.max_gpl <= 2) CGX_QUANT(k_quantize_fast<T, BITS, 2>);
+          else CGX_QUANT(k_quantize_fast<T, BITS, 4>);
+          break;
+        case kSub: CGX_QUANT(k_quantize_sub<T, BITS>); break;
+        case kGeneric: CGX_QUANT(k_quantize<T, BITS, true>); break;
+        default:  // kTwoPass: meta pass, then the arbitrary-bucket pack pass
+          CGX_QUANT(k_quantize<T, BITS, false>);
+          hipLaunchKernelGGL((k_pack_generic<T, BITS>), grid, block, 0,
+                             stream, descs, nslices, seed, stoch);
       }
     }
-    if (any_residual) {
-      hipLaunchKernelGGL((k_residual_q<T>), dim3(32), dim3(kThreads), 0,
-                         stream, descs, nslices, bits);
+    if (g.any_residual) {
+      hipLaunchKernelGGL((k_residual_q<T>), dim3(32), block, 0, stream, descs,
+                         nslices, g.bits);
     }
   }));
+#undef CGX_QUANT
 }
 
-void launch_quantize_fast(const QuantDesc* descs, const int64_t* cum,
-                          int nslices, int64_t total_buckets, DType dt,
-                          int bits, uint64_t seed, bool stochastic,
-                          hipStream_t stream, bool any_residual,
-                          int max_gpl) {
+void launch(const DequantGroup& g, const DequantDesc* descs, DType dt,
+            hipStream_t stream) {
+  const int nslices = static_cast<int>(g.descs.size());
   if (nslices <= 0) return;
-  const int grid = grid_for(std::max<int64_t>(total_buckets, 1),
-                            kThreads / kWave);
-  CGX_DISPATCH_T(dt, CGX_DISPATCH_BITS(bits, {
-    if (total_buckets > 0) {
-      if (max_gpl <= 2) {
-        hipLaunchKernelGGL((k_quantize_fast<T, BITS, 2>), dim3(grid),
-                           dim3(kThreads), 0, stream, descs, cum, nslices,
-                           total_buckets, seed, (int)stochastic);
+  const dim3 grid(grid_for(std::max<int64_t>(g.total_groups, 1), kThreads));
+  const dim3 block(kThreads);
+  CGX_DISPATCH_T(dt, CGX_DISPATCH_BITS(g.bits, {
+    if (g.total_groups > 0) {
+      if (g.kind == kFast) {
+        hipLaunchKernelGGL((k_dequant_fast<T, BITS>), grid, block, 0, stream,
+                           descs, nslices);
       } else {
-        hipLaunchKernelGGL((k_quantize_fast<T, BITS, 4>), dim3(grid),
-                           dim3(kThreads), 0, stream, descs, cum, nslices,
-                           total_buckets, seed, (int)stochastic);
+        hipLaunchKernelGGL((k_dequant<T, BITS>), grid, block, 0, stream,
+                           descs, nslices);
       }
     }
-    if (any_residual) {
-      hipLaunchKernelGGL((k_residual_q<T>), dim3(32), dim3(kThreads), 0,
-                         stream, descs, nslices, bits);
-    }
-  }));
-}
-
-void launch_quantize_sub(const QuantDesc* descs, const int64_t* cum,
-                         int nslices, int64_t total_buckets, DType dt,
-                         int bits, uint64_t seed, bool stochastic,
-                         hipStream_t stream, bool any_residual) {
-  if (nslices <= 0) return;
-  const int grid = grid_for(std::max<int64_t>(total_buckets, 1),
-                            kThreads / kWave);
-  CGX_DISPATCH_T(dt, CGX_DISPATCH_BITS(bits, {
-    if (total_buckets > 0) {
-      hipLaunchKernelGGL((k_quantize_sub<T, BITS>), dim3(grid),
-                         dim3(kThreads), 0, stream, descs, cum, nslices,
-                         total_buckets, seed, (int)stochastic);
-    }
-    if (any_residual) {
-      hipLaunchKernelGGL((k_residual_q<T>), dim3(32), dim3(kThreads), 0,
-                         stream, descs, nslices, bits);
-    }
-  }));
-}
-
-void launch_dequantize_batch(const DequantDesc* descs, const int64_t* cum,
-                             int nslices, int64_t total_groups, DType dt,
-                             int bits, hipStream_t stream,
-                             bool any_residual) {
-  if (nslices <= 0) return;
-  const int grid = grid_for(std::max<int64_t>(total_groups, 1), kThreads);
-  CGX_DISPATCH_T(dt, CGX_DISPATCH_BITS(bits, {
-    if (total_groups > 0) {
-      hipLaunchKernelGGL((k_dequant<T, BITS>), dim3(grid), dim3(kThreads), 0,
-                         stream, descs, cum, nslices, total_groups);
-    }
-    if (any_residual) {
-      hipLaunchKernelGGL((k_residual_d<T>), dim3(32), dim3(kThreads), 0,
-                         stream, descs, nslices, bits);
-    }
-  }));
-}
-
-void launch_dequantize_fast(const DequantDesc* descs, int nslices,
-                            int64_t total_groups, DType dt, int bits,
-                            hipStream_t stream, bool any_residual) {
-  if (nslices <= 0) return;
-  const int grid = grid_for(std::max<int64_t>(total_groups, 1), kThreads);
-  CGX_DISPATCH_T(dt, CGX_DISPATCH_BITS(bits, {
-    if (total_groups > 0) {
-      hipLaunchKernelGGL((k_dequant_fast<T, BITS>), dim3(grid),
-                         dim3(kThreads), 0, stream, descs, nslices);
-    }
-    if (any_residual) {
-      hipLaunchKernelGGL((k_residual_d<T>), dim3(32), dim3(kThreads), 0,
-                         stream, descs, nslices, bits);
+    if (g.any_residual) {
+      hipLaunchKernelGGL((k_residual_d<T>), dim3(32), block, 0, stream, descs,
+                         nslices, g.bits);
     }
   }));
 }

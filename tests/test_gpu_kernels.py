@@ -44,7 +44,7 @@ def test_quantize_matches_golden_bytes(dtype, bits, n, bucket):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("bits", [2, 4, 8])
+@pytest.mark.parametrize("bits", [1, 2, 3, 4, 5, 7, 8])
 @pytest.mark.parametrize("n,bucket", CASES)
 def test_dequantize_matches_golden(dtype, bits, n, bucket):
     from torch_cgx_amd import _C
@@ -55,6 +55,39 @@ def test_dequantize_matches_golden(dtype, bits, n, bucket):
     out = torch.empty(n, dtype=dtype, device=_dev())
     _C.dequantize(comp.to(_dev()), out, bits, bucket, False)
     assert torch.equal(out.cpu(), expected)
+
+
+def _add_in_T(base, dec):
+    return base + dec if base.dtype == torch.float32 \
+        else (base.float() + dec.float()).to(base.dtype)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("bits", [1, 3, 4, 8])
+@pytest.mark.parametrize("n,bucket", [(520, 512), (1000, 64), (4100, 4096),
+                                      (9, 7)])
+def test_unaligned_base_matches_golden(dtype, bits, n, bucket):
+    """Input and output one element past a 16B boundary: the whole slice
+    goes through the generic quantize kernel, and decode takes the
+    element-wise load/store paths."""
+    from torch_cgx_amd import _C
+    torch.manual_seed(n * bits + 2)
+    x = torch.randn(n).to(dtype)
+    base = torch.randn(n).to(dtype)
+    buf = torch.zeros(n + 9, dtype=dtype, device=_dev())
+    assert buf.data_ptr() % 16 == 0
+    buf[1:1 + n] = x.to(_dev())
+    comp_gold = golden.quantize(x, bits, bucket)
+    comp_gpu = _C.quantize(buf[1:1 + n], bits, bucket, False, 0)
+    assert torch.equal(comp_gpu.cpu(), comp_gold)
+    dec = golden.dequantize(comp_gold, n, dtype, bits, bucket)
+    for add, expected in [(False, dec), (True, _add_in_T(base, dec))]:
+        outbuf = torch.zeros(n + 9, dtype=dtype, device=_dev())
+        outbuf[1:1 + n] = base.to(_dev())
+        _C.dequantize(comp_gpu, outbuf[1:1 + n], bits, bucket, add)
+        assert torch.equal(outbuf[1:1 + n].cpu(), expected)
+        # nothing written outside the slice
+        assert outbuf[0].item() == 0 and not outbuf[1 + n:].any().item()
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
@@ -73,18 +106,27 @@ def test_dequantize_add_accumulates_in_T(dtype):
     assert torch.equal(out.cpu(), expected)
 
 
-@pytest.mark.parametrize("nsrc", [1, 3, 7])
-def test_dequantize_multi_matches_sequential(nsrc):
+@pytest.mark.parametrize("nsrc,n,bucket,dtype", [
+    pytest.param(1, 8192, 512, torch.float32, id="1"),
+    pytest.param(3, 8192, 512, torch.float32, id="3"),
+    pytest.param(7, 8192, 512, torch.float32, id="7"),
+    # 16-bit dtypes, incl. a ragged multi-source tail (1001 % 8 != 0)
+    pytest.param(3, 1001, 64, torch.float16, id="3-1001-64-fp16"),
+    pytest.param(3, 8192, 512, torch.float16, id="3-8192-512-fp16"),
+    pytest.param(3, 1001, 64, torch.bfloat16, id="3-1001-64-bf16"),
+    pytest.param(3, 8192, 512, torch.bfloat16, id="3-8192-512-bf16"),
+])
+def test_dequantize_multi_matches_sequential(nsrc, n, bucket, dtype):
     from torch_cgx_amd import _C
     torch.manual_seed(nsrc)
-    n, bits, bucket, dtype = 8192, 4, 512, torch.float32
+    bits = 4
     comps = []
     for s in range(nsrc):
-        x = torch.randn(n)
+        x = torch.randn(n).to(dtype)
         comps.append(golden.quantize(x, bits, bucket))
     stride = comps[0].numel()
     stacked = torch.stack(comps).to(_dev())
-    base = torch.randn(n)
+    base = torch.randn(n).to(dtype)
 
     # sequential T-precision accumulation on GPU (reference semantics)
     seq = base.to(_dev()).clone()
@@ -219,18 +261,34 @@ def test_skip_incomplete_dequant_add():
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("bits", [2, 4, 8])
 @pytest.mark.parametrize("n,bucket", [(4096, 512), (1000, 512), (131, 64),
-                                      (4096, 1024)])
+                                      (4096, 1024), (520, 512)])
 def test_error_feedback_matches_golden(dtype, bits, n, bucket):
+    _check_error_feedback(dtype, bits, n, bucket, offset=0)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("bits", [2, 4, 8])
+def test_error_feedback_unaligned_base(dtype, bits):
+    _check_error_feedback(dtype, bits, 1000, 64, offset=1)
+
+
+def _check_error_feedback(dtype, bits, n, bucket, offset):
+    """offset: elements between a 16B boundary and the start of x and fb."""
     from torch_cgx_amd import _C
     torch.manual_seed(n + bits)
     x = torch.randn(n).to(dtype)
     fb_gold = (torch.randn(n) * 0.1).to(dtype)
-    fb_gpu = fb_gold.clone().to(_dev())
+    xbuf = torch.zeros(n + 8, dtype=dtype, device=_dev())
+    fbbuf = torch.zeros(n + 8, dtype=dtype, device=_dev())
+    xg, fb_gpu = xbuf[offset:offset + n], fbbuf[offset:offset + n]
+    xg.copy_(x)
+    fb_gpu.copy_(fb_gold)
     comp_gold = golden.quantize_ef(x.clone(), fb_gold, bits, bucket)
-    comp_gpu = _C.quantize(x.to(_dev()), bits, bucket, False, 0, False,
-                           fb_gpu).cpu()
+    comp_gpu = _C.quantize(xg, bits, bucket, False, 0, False, fb_gpu).cpu()
     assert torch.equal(comp_gpu, comp_gold)
     assert torch.equal(fb_gpu.cpu(), fb_gold)
+    assert not fbbuf[:offset].any().item() and \
+        not fbbuf[offset + n:].any().item()
 
 
 def test_error_feedback_repeated_use():

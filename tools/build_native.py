@@ -16,6 +16,7 @@ from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SOURCES = [
     "csrc/quant_kernels.hip",
+    "csrc/compress.cc",
     "csrc/engine.cc",
     "csrc/transport.cc",
     "csrc/backend.cc",
