@@ -36,6 +36,27 @@ void check_single(const std::vector<at::Tensor>& ts) {
               "cgx: CUDA tensor must be contiguous");
 }
 
+// Join the communicator of `nranks` ranks whose ncclUniqueId travels through
+// the store under `key`: rank 0 of the communicator publishes it, the others
+// fetch it (the get blocks until the key is set).
+ncclComm_t init_comm(c10d::Store& store, const std::string& key, int nranks,
+                     int rank) {
+  ncclUniqueId id;
+  if (rank == 0) {
+    CGX_NCCL_CHECK(ncclGetUniqueId(&id));
+    store.set(key, std::vector<uint8_t>(
+                       reinterpret_cast<uint8_t*>(&id),
+                       reinterpret_cast<uint8_t*>(&id) + sizeof(id)));
+  } else {
+    auto v = store.get(key);
+    TORCH_CHECK(v.size() == sizeof(id), "cgx: bad nccl uid in store");
+    std::memcpy(&id, v.data(), sizeof(id));
+  }
+  ncclComm_t comm = nullptr;
+  CGX_NCCL_CHECK(ncclCommInitRank(&comm, nranks, id, rank));
+  return comm;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -135,12 +156,7 @@ ProcessGroupCGX::ProcessGroupCGX(c10::intrusive_ptr<c10d::Store> store,
 ProcessGroupCGX::~ProcessGroupCGX() {
   // drain pending work before tearing communicators down
   if (stream_) (void)hipStreamSynchronize(stream_->stream());
-  for (Engine* e : {engine_.get(), intra_engine_.get(),
-                    cross_engine_.get()}) {
-    if (!e) continue;
-    (void)hipStreamSynchronize(e->comm_stream());
-    (void)hipStreamSynchronize(e->deq_stream());
-  }
+  for_each_engine_stream([](hipStream_t s) { (void)hipStreamSynchronize(s); });
   if (intra_comm_) (void)ncclCommDestroy(intra_comm_);
   if (cross_comm_) (void)ncclCommDestroy(cross_comm_);
   if (comm_) (void)ncclCommDestroy(comm_);
@@ -157,19 +173,7 @@ void ProcessGroupCGX::lazyInit(at::Device device) {
   }
   device_index_ = device.index();
   c10::hip::HIPGuardMasqueradingAsCUDA guard(device_index_);
-  ncclUniqueId id;
-  if (rank_ == 0) {
-    CGX_NCCL_CHECK(ncclGetUniqueId(&id));
-    store_->set("cgx/nccl_uid",
-                std::vector<uint8_t>(reinterpret_cast<uint8_t*>(&id),
-                                     reinterpret_cast<uint8_t*>(&id) +
-                                         sizeof(id)));
-  } else {
-    auto v = store_->get("cgx/nccl_uid");
-    TORCH_CHECK(v.size() == sizeof(id), "cgx: bad nccl uid in store");
-    std::memcpy(&id, v.data(), sizeof(id));
-  }
-  CGX_NCCL_CHECK(ncclCommInitRank(&comm_, size_, id, rank_));
+  comm_ = init_comm(*store_, "cgx/nccl_uid", size_, rank_);
   tr_ = std::make_unique<RcclTransport>(comm_, rank_, size_);
   stream_ = c10::hip::getStreamFromPoolMasqueradingAsCUDA(
       /*isHighPriority=*/true, device_index_);
@@ -187,36 +191,15 @@ void ProcessGroupCGX::lazyInit(at::Device device) {
   if (topo_.n_nodes > 1 && topo_.uniform && topo_.local_size > 1 &&
       want_hier) {
     // intra communicator: ranks on this node
-    const std::string ikey = "cgx/intra_uid/" + std::to_string(topo_.node_id);
-    ncclUniqueId iid;
-    if (topo_.local_rank == 0) {
-      CGX_NCCL_CHECK(ncclGetUniqueId(&iid));
-      store_->set(ikey, std::vector<uint8_t>(
-                            reinterpret_cast<uint8_t*>(&iid),
-                            reinterpret_cast<uint8_t*>(&iid) + sizeof(iid)));
-    } else {
-      auto v = store_->get(ikey);
-      std::memcpy(&iid, v.data(), sizeof(iid));
-    }
-    CGX_NCCL_CHECK(ncclCommInitRank(&intra_comm_, topo_.local_size, iid,
-                                    topo_.local_rank));
+    intra_comm_ =
+        init_comm(*store_, "cgx/intra_uid/" + std::to_string(topo_.node_id),
+                  topo_.local_size, topo_.local_rank);
     intra_tr_ = std::make_unique<RcclTransport>(intra_comm_, topo_.local_rank,
                                                 topo_.local_size);
     // cross communicator: peers with the same local_rank on every node
-    const std::string ckey =
-        "cgx/cross_uid/" + std::to_string(topo_.local_rank);
-    ncclUniqueId cid;
-    if (topo_.node_id == 0) {
-      CGX_NCCL_CHECK(ncclGetUniqueId(&cid));
-      store_->set(ckey, std::vector<uint8_t>(
-                            reinterpret_cast<uint8_t*>(&cid),
-                            reinterpret_cast<uint8_t*>(&cid) + sizeof(cid)));
-    } else {
-      auto v = store_->get(ckey);
-      std::memcpy(&cid, v.data(), sizeof(cid));
-    }
-    CGX_NCCL_CHECK(
-        ncclCommInitRank(&cross_comm_, topo_.n_nodes, cid, topo_.node_id));
+    cross_comm_ =
+        init_comm(*store_, "cgx/cross_uid/" + std::to_string(topo_.local_rank),
+                  topo_.n_nodes, topo_.node_id);
     cross_tr_ = std::make_unique<RcclTransport>(cross_comm_, topo_.node_id,
                                                 topo_.n_nodes);
     intra_engine_ = std::make_unique<Engine>(topo_.local_rank,
@@ -260,14 +243,10 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::collective(
   // passthrough op behind any compressed-allreduce traffic still queued on
   // the engine's comm/decode streams (the compressed path itself chains the
   // other direction through start_ev_, so ordering is total).
-  for (Engine* e : {engine_.get(), intra_engine_.get(),
-                    cross_engine_.get()}) {
-    if (!e) continue;
-    for (hipStream_t s : {e->comm_stream(), e->deq_stream()}) {
-      CGX_HIP_CHECK(hipEventRecord(start_ev_, s));
-      CGX_HIP_CHECK(hipStreamWaitEvent(stream_->stream(), start_ev_, 0));
-    }
-  }
+  for_each_engine_stream([&](hipStream_t s) {
+    CGX_HIP_CHECK(hipEventRecord(start_ev_, s));
+    CGX_HIP_CHECK(hipStreamWaitEvent(stream_->stream(), start_ev_, 0));
+  });
   c10::hip::HIPStreamGuardMasqueradingAsCUDA sguard(stream_->unwrap());
   fn(stream_->stream());
   for (const auto& t : outputs) {
@@ -288,8 +267,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::allreduce(
   check_single(tensors);
   at::Tensor t = tensors[0];
   if (!t.is_cuda()) {
-    TORCH_CHECK(cpu_, "cgx: no CPU delegate backend available");
-    return cpu_->allreduce(tensors, opts);
+    return cpu_delegate().allreduce(tensors, opts);
   }
   const bool compressible =
       opts.reduceOp == c10d::ReduceOp::SUM &&
@@ -337,21 +315,16 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::allreduce(
     auto fin_masq = c10::hip::getStreamFromExternalMasqueradingAsCUDA(
         fin, device_index_);
     c10::hip::HIPStreamGuardMasqueradingAsCUDA sguard(fin_masq.unwrap());
-    std::vector<hipStream_t> touched{stream_->stream()};
-    for (Engine* e : {engine_.get(), intra_engine_.get(),
-                      cross_engine_.get()}) {
-      if (!e) continue;
-      touched.push_back(e->comm_stream());
-      touched.push_back(e->deq_stream());
-    }
-    for (hipStream_t s : touched) {
-      if (!s) continue;
+    auto touch = [&](hipStream_t s) {
+      if (!s) return;
       c10::hip::HIPCachingAllocatorMasqueradingAsCUDA::
           recordStreamMasqueradingAsCUDA(
               t.storage().data_ptr(),
               c10::hip::getStreamFromExternalMasqueradingAsCUDA(
                   s, device_index_));
-    }
+    };
+    touch(stream_->stream());
+    for_each_engine_stream(touch);
     auto work = c10::make_intrusive<WorkCGX>(rank_, c10d::OpType::ALLREDUCE,
                                              t.device(), tensors,
                                              "cgx:allreduce_compressed");
@@ -372,8 +345,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::allreduce_coalesced(
     const c10d::AllreduceCoalescedOptions& opts) {
   TORCH_CHECK(!tensors.empty());
   if (!tensors[0].is_cuda()) {
-    TORCH_CHECK(cpu_, "cgx: no CPU delegate backend available");
-    return cpu_->allreduce_coalesced(tensors, opts);
+    return cpu_delegate().allreduce_coalesced(tensors, opts);
   }
   auto op = opts.reduceOp;
   return collective(tensors, tensors[0].device(), c10d::OpType::COALESCED,
@@ -394,8 +366,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::broadcast(
   check_single(tensors);
   at::Tensor t = tensors[0];
   if (!t.is_cuda()) {
-    TORCH_CHECK(cpu_, "cgx: no CPU delegate backend available");
-    return cpu_->broadcast(tensors, opts);
+    return cpu_delegate().broadcast(tensors, opts);
   }
   const int root = static_cast<int>(opts.rootRank);
   return collective(tensors, t.device(), c10d::OpType::BROADCAST,
@@ -412,8 +383,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::reduce(
   check_single(tensors);
   at::Tensor t = tensors[0];
   if (!t.is_cuda()) {
-    TORCH_CHECK(cpu_, "cgx: no CPU delegate backend available");
-    return cpu_->reduce(tensors, opts);
+    return cpu_delegate().reduce(tensors, opts);
   }
   const int root = static_cast<int>(opts.rootRank);
   auto op = opts.reduceOp;
@@ -434,8 +404,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::allgather(
   TORCH_CHECK(outputs.size() == 1 && (int)outputs[0].size() == size_);
   at::Tensor in = inputs[0];
   if (!in.is_cuda()) {
-    TORCH_CHECK(cpu_, "cgx: no CPU delegate backend available");
-    return cpu_->allgather(outputs, inputs, opts);
+    return cpu_delegate().allgather(outputs, inputs, opts);
   }
   auto outs = outputs[0];
   return collective(outs, in.device(), c10d::OpType::ALLGATHER,
@@ -462,8 +431,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::_allgather_base(
     at::Tensor& output, at::Tensor& input,
     const c10d::AllgatherOptions& opts) {
   if (!input.is_cuda()) {
-    TORCH_CHECK(cpu_, "cgx: no CPU delegate backend available");
-    return cpu_->_allgather_base(output, input, opts);
+    return cpu_delegate()._allgather_base(output, input, opts);
   }
   TORCH_CHECK(output.numel() == input.numel() * size_);
   at::Tensor in = input, out = output;
@@ -481,8 +449,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::gather(
   check_single(inputs);
   at::Tensor in = inputs[0];
   if (!in.is_cuda()) {
-    TORCH_CHECK(cpu_, "cgx: no CPU delegate backend available");
-    return cpu_->gather(outputs, inputs, opts);
+    return cpu_delegate().gather(outputs, inputs, opts);
   }
   const int root = static_cast<int>(opts.rootRank);
   std::vector<at::Tensor> outs =
@@ -518,8 +485,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::scatter(
   check_single(outputs);
   at::Tensor out = outputs[0];
   if (!out.is_cuda()) {
-    TORCH_CHECK(cpu_, "cgx: no CPU delegate backend available");
-    return cpu_->scatter(outputs, inputs, opts);
+    return cpu_delegate().scatter(outputs, inputs, opts);
   }
   const int root = static_cast<int>(opts.rootRank);
   std::vector<at::Tensor> ins =
@@ -555,8 +521,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::reduce_scatter(
   check_single(outputs);
   at::Tensor out = outputs[0];
   if (!out.is_cuda()) {
-    TORCH_CHECK(cpu_, "cgx: no CPU delegate backend available");
-    return cpu_->reduce_scatter(outputs, inputs, opts);
+    return cpu_delegate().reduce_scatter(outputs, inputs, opts);
   }
   TORCH_CHECK((int)inputs[0].size() == size_);
   // flatten inputs into one contiguous buffer, then ncclReduceScatter
@@ -582,8 +547,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::_reduce_scatter_base(
     at::Tensor& output, at::Tensor& input,
     const c10d::ReduceScatterOptions& opts) {
   if (!input.is_cuda()) {
-    TORCH_CHECK(cpu_, "cgx: no CPU delegate backend available");
-    return cpu_->_reduce_scatter_base(output, input, opts);
+    return cpu_delegate()._reduce_scatter_base(output, input, opts);
   }
   TORCH_CHECK(input.numel() == output.numel() * size_);
   at::Tensor in = input, out = output;
@@ -602,10 +566,9 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::alltoall_base(
     std::vector<int64_t>& outputSplitSizes,
     std::vector<int64_t>& inputSplitSizes, const c10d::AllToAllOptions&) {
   if (!input.is_cuda()) {
-    TORCH_CHECK(cpu_, "cgx: no CPU delegate backend available");
     std::vector<int64_t> os = outputSplitSizes, is = inputSplitSizes;
     c10d::AllToAllOptions o;
-    return cpu_->alltoall_base(output, input, os, is, o);
+    return cpu_delegate().alltoall_base(output, input, os, is, o);
   }
   at::Tensor in = input, out = output;
   std::vector<int64_t> osplit = outputSplitSizes, isplit = inputSplitSizes;
@@ -652,7 +615,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::alltoall(
     const c10d::AllToAllOptions&) {
   TORCH_CHECK((int)outputs.size() == size_ && (int)inputs.size() == size_);
   if (!inputs[0].is_cuda()) {
-    TORCH_CHECK(cpu_, "cgx: no CPU delegate backend available");
+    c10d::Backend& cpu = cpu_delegate();
     // gloo has no alltoall; compose it from ordered pairwise gloo p2p
     // (deadlock-free: the lower rank of each pair sends first; the
     // reference used MPI_Alltoall here, ProcessGroupCGX.cc:659)
@@ -662,15 +625,15 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::alltoall(
       std::vector<at::Tensor> st{inputs[p].contiguous()};
       std::vector<at::Tensor> rt{outputs[p]};
       if (rank_ < p) {
-        cpu_->send(st, p, 0)->wait();
-        cpu_->recv(rt, p, 0)->wait();
+        cpu.send(st, p, 0)->wait();
+        cpu.recv(rt, p, 0)->wait();
       } else {
-        cpu_->recv(rt, p, 0)->wait();
-        cpu_->send(st, p, 0)->wait();
+        cpu.recv(rt, p, 0)->wait();
+        cpu.send(st, p, 0)->wait();
       }
     }
     c10d::BarrierOptions bo;
-    return cpu_->barrier(bo);
+    return cpu.barrier(bo);
   }
   std::vector<at::Tensor> ins = inputs, outs = outputs;
   return collective(outputs, inputs[0].device(), c10d::OpType::ALLTOALL,
@@ -714,8 +677,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::send(
   check_single(tensors);
   at::Tensor t = tensors[0];
   if (!t.is_cuda()) {
-    TORCH_CHECK(cpu_, "cgx: no CPU delegate backend available");
-    return cpu_->send(tensors, dstRank, tag);
+    return cpu_delegate().send(tensors, dstRank, tag);
   }
   if (p2p_anysource()) {
     TORCH_CHECK(cpu_, "cgx: CGX_P2P_ANYSOURCE requires the CPU delegate");
@@ -745,8 +707,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::recv(
   check_single(tensors);
   at::Tensor t = tensors[0];
   if (!t.is_cuda()) {
-    TORCH_CHECK(cpu_, "cgx: no CPU delegate backend available");
-    return cpu_->recv(tensors, srcRank, tag);
+    return cpu_delegate().recv(tensors, srcRank, tag);
   }
   if (p2p_anysource()) {
     // consume this sender's announcement to keep the pairing in lockstep
@@ -766,8 +727,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::recvAnysource(
     std::vector<at::Tensor>& tensors, int tag) {
   check_single(tensors);
   if (!tensors[0].is_cuda()) {
-    TORCH_CHECK(cpu_, "cgx: no CPU delegate backend available");
-    return cpu_->recvAnysource(tensors, tag);
+    return cpu_delegate().recvAnysource(tensors, tag);
   }
   TORCH_CHECK(p2p_anysource(),
               "cgx: recvAnysource for GPU tensors requires "
@@ -800,12 +760,8 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::barrier(
   if (comm_) {
     std::lock_guard<std::mutex> lock(mu_);
     CGX_HIP_CHECK(hipStreamSynchronize(stream_->stream()));
-    for (Engine* e : {engine_.get(), intra_engine_.get(),
-                      cross_engine_.get()}) {
-      if (!e) continue;
-      CGX_HIP_CHECK(hipStreamSynchronize(e->comm_stream()));
-      CGX_HIP_CHECK(hipStreamSynchronize(e->deq_stream()));
-    }
+    for_each_engine_stream(
+        [](hipStream_t s) { CGX_HIP_CHECK(hipStreamSynchronize(s)); });
   }
   if (cpu_) {
     c10d::BarrierOptions o = opts;

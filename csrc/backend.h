@@ -138,6 +138,23 @@ class ProcessGroupCGX : public c10d::Backend {
                                             at::Device device,
                                             c10d::OpType op, Fn&& fn);
 
+  // fn(stream) for the comm and deq stream of every live engine
+  template <typename Fn>
+  void for_each_engine_stream(Fn&& fn) const {
+    for (Engine* e : {engine_.get(), intra_engine_.get(),
+                      cross_engine_.get()}) {
+      if (!e) continue;
+      fn(e->comm_stream());
+      fn(e->deq_stream());
+    }
+  }
+
+  // the CPU (gloo) delegate; CPU tensors cannot be served without one
+  c10d::Backend& cpu_delegate() const {
+    TORCH_CHECK(cpu_, "cgx: no CPU delegate backend available");
+    return *cpu_;
+  }
+
   c10::intrusive_ptr<c10d::Store> store_;
   c10::intrusive_ptr<c10d::Backend> cpu_;
   ncclComm_t comm_ = nullptr;

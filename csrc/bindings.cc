@@ -14,7 +14,9 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 
 #include <cstring>
+#include <functional>
 #include <thread>
+#include <tuple>
 
 #include "backend.h"
 #include "engine.h"
@@ -22,6 +24,40 @@
 
 namespace cgx {
 namespace {
+
+// Rank-thread harness of the loopback seams: one quantize stream and one
+// thread per rank, GIL released.  A rank that throws stores its error and
+// calls `abort` (poison the hubs so no peer blocks in join); the first error
+// is rethrown once every thread has joined and the device has drained.
+void run_rank_threads(int ws, int dev,
+                      const std::function<void(int, hipStream_t)>& body,
+                      const std::function<void()>& abort) {
+  std::vector<hipStream_t> qs(ws, nullptr);
+  for (auto& s : qs)
+    CGX_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  std::vector<std::exception_ptr> errs(ws);
+  {
+    py::gil_scoped_release nogil;
+    std::vector<std::thread> th;
+    for (int r = 0; r < ws; r++) {
+      th.emplace_back([&, r] {
+        try {
+          c10::hip::HIPGuardMasqueradingAsCUDA g(dev);
+          body(r, qs[r]);
+        } catch (...) {
+          errs[r] = std::current_exception();
+          abort();  // unblock peers so join() cannot hang
+        }
+      });
+    }
+    for (auto& t : th) t.join();
+  }
+  (void)hipDeviceSynchronize();  // loopback events/copies fully retired
+  for (auto s : qs)
+    if (s) (void)hipStreamDestroy(s);
+  for (int r = 0; r < ws; r++)
+    if (errs[r]) std::rethrow_exception(errs[r]);
+}
 
 // Drive the REAL engine code at world size ws on ONE GPU: `buckets[r]` is
 // rank r's flat bucket; ws Engine instances (each with its own streams,
@@ -48,38 +84,20 @@ void run_loopback(const std::vector<at::Tensor>& tensors,
   LoopbackHub hub(ws);
   std::vector<std::unique_ptr<Engine>> engines;
   std::vector<std::unique_ptr<LoopbackTransport>> trs;
-  std::vector<hipStream_t> qs(ws, nullptr);
   for (int r = 0; r < ws; r++) {
     engines.push_back(std::make_unique<Engine>(r, ws));
     trs.push_back(std::make_unique<LoopbackTransport>(&hub, r));
-    CGX_HIP_CHECK(hipStreamCreateWithFlags(&qs[r], hipStreamNonBlocking));
   }
-  std::vector<std::exception_ptr> errs(ws);
-  {
-    py::gil_scoped_release nogil;
-    std::vector<std::thread> th;
-    for (int r = 0; r < ws; r++) {
-      th.emplace_back([&, r] {
-        try {
-          c10::hip::HIPGuardMasqueradingAsCUDA g(dev);
-          hipStream_t fin = body(*engines[r], trs[r].get(), qs[r], r);
-          CGX_HIP_CHECK(hipStreamSynchronize(fin));
-          CGX_HIP_CHECK(hipStreamSynchronize(qs[r]));
-          CGX_HIP_CHECK(hipStreamSynchronize(engines[r]->comm_stream()));
-          CGX_HIP_CHECK(hipStreamSynchronize(engines[r]->deq_stream()));
-        } catch (...) {
-          errs[r] = std::current_exception();
-          hub.abort();  // unblock peers so join() cannot hang
-        }
-      });
-    }
-    for (auto& t : th) t.join();
-  }
-  (void)hipDeviceSynchronize();  // loopback events/copies fully retired
-  for (auto s : qs)
-    if (s) (void)hipStreamDestroy(s);
-  for (int r = 0; r < ws; r++)
-    if (errs[r]) std::rethrow_exception(errs[r]);
+  run_rank_threads(
+      ws, dev,
+      [&](int r, hipStream_t qs) {
+        hipStream_t fin = body(*engines[r], trs[r].get(), qs, r);
+        CGX_HIP_CHECK(hipStreamSynchronize(fin));
+        CGX_HIP_CHECK(hipStreamSynchronize(qs));
+        CGX_HIP_CHECK(hipStreamSynchronize(engines[r]->comm_stream()));
+        CGX_HIP_CHECK(hipStreamSynchronize(engines[r]->deq_stream()));
+      },
+      [&] { hub.abort(); });
 }
 
 void py_loopback_allreduce(std::vector<at::Tensor> buckets) {
@@ -155,54 +173,38 @@ void py_loopback_hierarchical(std::vector<at::Tensor> buckets,
   std::vector<std::unique_ptr<LoopbackTransport>> intra_tr;
   std::vector<std::unique_ptr<Engine>> cross_eng;    // per node (leader)
   std::vector<std::unique_ptr<LoopbackTransport>> cross_tr;
-  std::vector<hipStream_t> qs(ws, nullptr);
   for (int r = 0; r < ws; r++) {
     const int nd = r / (int)local_size;
     const int lr = r % (int)local_size;
     intra_eng.push_back(std::make_unique<Engine>(lr, (int)local_size));
     intra_tr.push_back(
         std::make_unique<LoopbackTransport>(intra_hubs[nd].get(), lr));
-    CGX_HIP_CHECK(hipStreamCreateWithFlags(&qs[r], hipStreamNonBlocking));
   }
   for (int nd = 0; nd < nodes; nd++) {
     cross_eng.push_back(
         std::make_unique<Engine>(nd, nodes, /*is_cross=*/true));
     cross_tr.push_back(std::make_unique<LoopbackTransport>(&cross_hub, nd));
   }
-  std::vector<std::exception_ptr> errs(ws);
-  {
-    py::gil_scoped_release nogil;
-    std::vector<std::thread> th;
-    for (int r = 0; r < ws; r++) {
-      th.emplace_back([&, r] {
-        try {
-          c10::hip::HIPGuardMasqueradingAsCUDA g(dev);
-          const int nd = r / (int)local_size;
-          const int lr = r % (int)local_size;
-          hipStream_t fin = intra_eng[r]->allreduce(
-              buckets[r], intra_tr[r].get(), qs[r], &info, matched);
-          if (lr == 0) {
-            fin = cross_eng[nd]->allreduce(buckets[r], cross_tr[nd].get(),
-                                           fin, &info, matched);
-          }
-          fin = intra_eng[r]->broadcast(buckets[r], /*root=*/0,
-                                        intra_tr[r].get(), fin);
-          CGX_HIP_CHECK(hipStreamSynchronize(fin));
-          CGX_HIP_CHECK(hipStreamSynchronize(qs[r]));
-        } catch (...) {
-          errs[r] = std::current_exception();
-          for (auto& h : intra_hubs) h->abort();
-          cross_hub.abort();
+  run_rank_threads(
+      ws, dev,
+      [&](int r, hipStream_t qs) {
+        const int nd = r / (int)local_size;
+        const int lr = r % (int)local_size;
+        hipStream_t fin = intra_eng[r]->allreduce(
+            buckets[r], intra_tr[r].get(), qs, &info, matched);
+        if (lr == 0) {
+          fin = cross_eng[nd]->allreduce(buckets[r], cross_tr[nd].get(), fin,
+                                         &info, matched);
         }
+        fin = intra_eng[r]->broadcast(buckets[r], /*root=*/0,
+                                      intra_tr[r].get(), fin);
+        CGX_HIP_CHECK(hipStreamSynchronize(fin));
+        CGX_HIP_CHECK(hipStreamSynchronize(qs));
+      },
+      [&] {
+        for (auto& h : intra_hubs) h->abort();
+        cross_hub.abort();
       });
-    }
-    for (auto& t : th) t.join();
-  }
-  (void)hipDeviceSynchronize();
-  for (auto s : qs)
-    if (s) (void)hipStreamDestroy(s);
-  for (int r = 0; r < ws; r++)
-    if (errs[r]) std::rethrow_exception(errs[r]);
 }
 
 // Copy a routed group's descs (followed by cum, if any) to the device.
@@ -360,9 +362,74 @@ std::pair<std::vector<int64_t>, std::vector<int64_t>> py_partition(
     int64_t num_elements, int64_t world_size,
     std::vector<int64_t> layer_numels, int64_t esize) {
   std::vector<int64_t> offs, szs;
-  Engine::partition(num_elements, (int)world_size, layer_numels, (int)esize,
-                    &offs, &szs);
+  partition(num_elements, (int)world_size, layer_numels, (int)esize, &offs,
+            &szs);
   return {offs, szs};
+}
+
+// Test seams for chunk planning (plan.h): pure host code.  Pointers travel
+// as ints with base 0, so every `data` is a byte offset into the bucket.
+// (byte_off, numel, bits, bucket)
+using PyView = std::tuple<uint64_t, int64_t, int, int>;
+std::vector<LayerView> to_views(const std::vector<PyView>& views) {
+  std::vector<LayerView> out;
+  for (const auto& [off, numel, bits, bucket] : views)
+    out.push_back(LayerView{reinterpret_cast<char*>(off), numel, bits, bucket});
+  return out;
+}
+
+// -> (uncomp [(byte_off, count)], chunks [[(byte_off, numel, bits, bucket)]])
+py::tuple py_plan_bucket(const std::vector<int64_t>& layer_numels,
+                         const std::vector<std::pair<int, int>>& layer_cfgs,
+                         at::ScalarType st, int64_t fusion_bytes,
+                         int64_t min_elems, double fake_ratio, bool dummy) {
+  TORCH_CHECK(layer_numels.size() == layer_cfgs.size(),
+              "plan_bucket: one (bits, bucket_size) per layer");
+  const int es = elem_size(dtype_of(st));
+  EngineConfig cfg;
+  cfg.fusion_bytes = fusion_bytes;
+  cfg.min_elems = min_elems;
+  cfg.fake_ratio = fake_ratio;
+  cfg.dummy = dummy;
+  std::vector<LayerView> views;
+  int64_t off = 0;
+  for (size_t i = 0; i < layer_numels.size(); i++) {
+    views.push_back(LayerView{reinterpret_cast<char*>(off * es),
+                              layer_numels[i], layer_cfgs[i].first,
+                              layer_cfgs[i].second});
+    off += layer_numels[i];
+  }
+  const BucketPlan bp = plan_bucket(views, cfg, es);
+  py::list uncomp, chunks;
+  for (const auto& [ptr, cnt] : bp.uncomp)
+    uncomp.append(py::make_tuple(reinterpret_cast<uint64_t>(ptr), cnt));
+  for (const auto& chunk : bp.chunks) {
+    py::list vs;
+    for (const LayerView& v : chunk)
+      vs.append(py::make_tuple(reinterpret_cast<uint64_t>(v.data), v.numel,
+                               v.bits, v.bucket_size));
+    chunks.append(vs);
+  }
+  return py::make_tuple(uncomp, chunks);
+}
+
+// views: [(byte_off, numel, bits, bucket)] ->
+// (offs, szs, comp, rs [[(byte_off, n, bits, bucket, comp_off, skip, fb_off)]])
+py::tuple py_plan_chunk(const std::vector<PyView>& views, at::ScalarType st,
+                        int ws, bool skip_incomplete) {
+  TORCH_CHECK(ws >= 1, "plan_chunk: ws >= 1");
+  const ChunkPlan pl =
+      plan_chunk(to_views(views), dtype_of(st), ws, skip_incomplete);
+  py::list rs;
+  for (const auto& slices : pl.rs) {
+    py::list r;
+    for (const Slice& s : slices)
+      r.append(py::make_tuple(reinterpret_cast<uint64_t>(s.data), s.n, s.bits,
+                              s.bucket, s.comp_off, s.skip_incomplete,
+                              s.fb_off));
+    rs.append(r);
+  }
+  return py::make_tuple(pl.offs, pl.szs, pl.comp, rs);
 }
 
 void py_register_layer(int64_t bucket_idx, int64_t layer_idx, int64_t numel,
@@ -485,6 +552,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bits"), py::arg("bucket_size"),
         py::arg("skip_incomplete") = false);
   m.def("partition", &cgx::py_partition);
+  m.def("plan_bucket", &cgx::py_plan_bucket, py::arg("layer_numels"),
+        py::arg("layer_cfgs"), py::arg("dtype"), py::arg("fusion_bytes"),
+        py::arg("min_elems"), py::arg("fake_ratio") = 1.0,
+        py::arg("dummy") = false,
+        "Test seam: the bucket plan for layers laid out back to back from "
+        "byte offset 0 -> (uncomp [(byte_off, count)], chunks [[(byte_off, "
+        "numel, bits, bucket)]]).");
+  m.def("plan_chunk", &cgx::py_plan_chunk, py::arg("views"), py::arg("dtype"),
+        py::arg("ws"), py::arg("skip_incomplete") = false,
+        "Test seam: the rank plan of one chunk [(byte_off, numel, bits, "
+        "bucket)] -> (offs, szs, comp, rs [[(byte_off, n, bits, bucket, "
+        "comp_off, skip_incomplete, fb_off)]]).");
   m.def("route_quantize", &cgx::py_route_quantize, py::arg("slices"),
         "Test seam: the launch router's quantize plan for "
         "[(in, out, fb, n, bits, bucket, skip_incomplete)] (pointers as "

@@ -1,5 +1,7 @@
-// Compression engine: layer registry, fusion chunking, rank partitioning and
-// the compressed Scatter-Reduce-AllGather allreduce over RCCL/xGMI.
+// Compression engine: the streams, events and staging that execute the
+// compressed Scatter-Reduce-AllGather / Ring allreduce over RCCL/xGMI.  What
+// is reduced where is decided by pure host code: the layer registry
+// (registry.h), the env config (config.h) and chunk planning (plan.h).
 //
 // This is the MI355X-native equivalent of the reference's
 // mpi_allreduce_operations + compressor + reducer stack
@@ -14,105 +16,20 @@
 #include <ATen/ATen.h>
 #include <rccl/rccl.h>
 
-#include "transport.h"
-
 #include <cstdint>
 #include <map>
-#include <mutex>
-#include <tuple>
-#include <unordered_map>
+#include <utility>
 #include <vector>
 
+#include "check.h"
 #include "compress.h"
+#include "config.h"
+#include "phase_timer.h"
+#include "plan.h"
+#include "registry.h"
+#include "transport.h"
 
 namespace cgx {
-
-#define CGX_HIP_CHECK(cmd)                                              \
-  do {                                                                  \
-    hipError_t e_ = (cmd);                                              \
-    TORCH_CHECK(e_ == hipSuccess, "cgx HIP error: ", hipGetErrorString(e_)); \
-  } while (0)
-
-#define CGX_NCCL_CHECK(cmd)                                              \
-  do {                                                                   \
-    ncclResult_t r_ = (cmd);                                             \
-    TORCH_CHECK(r_ == ncclSuccess, "cgx RCCL error: ", ncclGetErrorString(r_)); \
-  } while (0)
-
-struct LayerConfig {
-  int bits = 32;
-  int bucket_size = 512;
-};
-
-// Process-global layer registry (parity with the reference's static
-// MPIAllReduce_Operation::RegisterLayer / Compressor config registry,
-// mpi_allreduce_operations.h:37-49, compressor.h:93-107).
-class Registry {
- public:
-  struct BucketInfo {
-    int idx = -1;
-    std::vector<int64_t> numels;
-    std::vector<LayerConfig> cfgs;
-    int64_t total = 0;
-  };
-
-  static Registry& get();
-
-  void register_layer(int bucket_idx, int layer_idx, int64_t numel, int bits,
-                      int bucket_size);
-  void set_bits(int bucket_idx, int layer_idx, int bits);
-  void set_bucket_size(int bucket_idx, int layer_idx, int bucket_size);
-  void clear();
-  bool empty();
-
-  // Match the next allreduce call (of `numel` total elements) to a
-  // registered bucket, cycling through registration order (the reference's
-  // modulo-cursor, extractLayers, mpi_allreduce_operations.cc:257-285 —
-  // hardened twice over: a bucket only matches if its total numel agrees,
-  // and once a flat-bucket storage pointer `key` has matched a bucket, the
-  // pointer is bound to it so later calls resolve by identity even when two
-  // buckets share a total but differ in layer layout (DDP reuses its flat
-  // gradient buffers, so the pointer is stable until a bucket rebuild — at
-  // which point the total check unbinds it and the cursor re-learns).
-  // Returns a copy (thread safety) or nullopt-like empty BucketInfo.
-  bool next(int64_t numel, const void* key, BucketInfo* out);
-  std::vector<BucketInfo> snapshot();
-
- private:
-  std::mutex mu_;
-  std::vector<BucketInfo> order_;
-  std::unordered_map<int, size_t> by_idx_;
-  std::unordered_map<const void*, size_t> bound_;
-  size_t cursor_ = 0;
-};
-
-// A contiguous compressible piece of the flat bucket tensor.
-struct LayerView {
-  char* data;
-  int64_t numel;
-  int bits;
-  int bucket_size;
-};
-
-struct EngineConfig {
-  int64_t fusion_bytes = 64ll << 20;
-  int64_t min_elems = 16;
-  int default_bits = 32;
-  int default_bucket = 512;
-  bool stochastic = true;
-  bool ring = false;        // CGX_INNER_REDUCTION_TYPE=Ring (default SRA)
-  bool cross_ring = true;   // CGX_CROSS_REDUCTION_TYPE (default Ring, like
-                            // the reference's cross-node default,
-                            // mpi_allreduce_operations.cc:96-115)
-  bool debug_a2a = false;   // CGX_DEBUG_ALL_TO_ALL_REDUCTION: brute-force
-                            // all-to-all fallback for fault isolation
-  double fake_ratio = 1.0;  // CGX_COMPRESSION_FAKE_RATIO (bandwidth expt)
-  bool skip_incomplete = false;  // CGX_COMPRESSION_SKIP_INCOMPLETE_BUCKETS
-  bool dummy = false;  // CGX_DEBUG_DUMMY_COMPRESSION: force uncompressed
-  bool intra_compress = true;  // CGX_INTRA_COMPRESS
-  bool error_feedback = false;  // CGX_ERROR_FEEDBACK (needs bucket%8==0)
-  static EngineConfig from_env();  // re-read every bucket like the reference
-};
 
 // Pinned-host + device descriptor upload arena with an event-guarded ring so
 // batches can be queued back-to-back without host/device races.
@@ -176,24 +93,7 @@ class Engine {
   hipStream_t broadcast(at::Tensor t, int root, Transport* tr,
                         hipStream_t qs);
 
-  // Mirror of the partition walk (reference Quantizer::GetSizesAndOffsets,
-  // compressor.cc:265-299); exposed for tests via bindings.
-  static void partition(int64_t num_elements, int world_size,
-                        const std::vector<int64_t>& layer_numels, int esize,
-                        std::vector<int64_t>* offsets,
-                        std::vector<int64_t>* sizes);
-
  private:
-  struct Slice {  // one layer piece inside one rank chunk
-    char* data;
-    int64_t n;
-    int bits;
-    int bucket;
-    int64_t comp_off;  // byte offset of this slice in the chunk's comp stream
-    bool skip_incomplete = false;
-    int64_t fb_off = 0;  // element offset in the chunk's error-feedback buf
-  };
-
   // Double-buffered staging so chunk c+1's quantize (on qs) can start while
   // chunk c's traffic/decode (on comm/deq streams) still reads its slot.
   struct StagingSlot {
@@ -201,15 +101,6 @@ class Engine {
     hipEvent_t done_ev = nullptr;  // recorded on deq stream at chunk end
     bool recorded = false;
   };
-
-  struct ChunkPlan {
-    std::vector<std::vector<Slice>> rs;  // per-rank slice lists
-    std::vector<int64_t> comp;           // per-rank compressed bytes
-    std::vector<int64_t> offs, szs;
-    int64_t n = 0;
-  };
-  ChunkPlan plan(const std::vector<LayerView>& views, DType dt,
-                 bool skip_incomplete);
 
   // fb_key: stable identity of this (bucket, chunk) for the error-feedback
   // residual store — (bucket_idx << 20 | chunk ordinal) when the registry
@@ -253,32 +144,9 @@ class Engine {
                    int64_t src_stride, int nsrc, bool add, DType dt,
                    hipStream_t stream);
 
-  // CGX_TIMINGS=1: per-phase GPU timing of each SRA chunk (quantize /
-  // round-1 comm / decode+requantize / round-2 comm / final decode),
-  // aggregated and printed every 50 chunks (the reference had no
-  // timers at all).
-  struct PhaseTimer {
-    static constexpr int kRing = 4;
-    static constexpr int kEv = 6;
-    hipEvent_t ev[kRing][kEv] = {};
-    bool pending[kRing] = {};
-    int cur = 0;
-    double sum_ms[kEv - 1] = {};
-    int64_t count = 0;
-    bool inited = false;
-  };
-  PhaseTimer timer_;
-  void timer_begin(hipStream_t qs, bool enabled);
-  void timer_mark(int idx, hipStream_t stream);  // idx 1..5
-  void timer_finish();
-  void timer_drain();  // destructor: flush in-flight slots + final print
-  void timer_collect(int slot);  // fold one finished slot into the sums
-  void timer_print(const char* suffix) const;  // the five-phase line
-  bool timing_ = false;
-  int timer_slot_ = -1;
-
   int rank_, size_;
   bool is_cross_ = false;
+  PhaseTimer timer_;  // CGX_TIMINGS=1: per-phase timing of SRA chunks
   at::Tensor staging_;
   StagingSlot slots_[2];
   int slot_cur_ = 0;

@@ -3,7 +3,7 @@
 
 #include <ATen/ATen.h>
 
-#include "engine.h"  // CGX_HIP_CHECK / CGX_NCCL_CHECK
+#include "check.h"
 
 namespace cgx {
 

@@ -17,13 +17,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SOURCES = [
     "csrc/quant_kernels.hip",
     "csrc/compress.cc",
+    "csrc/config.cc",
+    "csrc/registry.cc",
+    "csrc/plan.cc",
+    "csrc/phase_timer.cc",
     "csrc/engine.cc",
     "csrc/transport.cc",
     "csrc/backend.cc",
     "csrc/bindings.cc",
 ]
-HEADERS = ["csrc/compress.h", "csrc/engine.h", "csrc/backend.h",
-           "csrc/transport.h"]
+HEADERS = ["csrc/compress.h", "csrc/check.h", "csrc/config.h",
+           "csrc/registry.h", "csrc/plan.h", "csrc/phase_timer.h",
+           "csrc/engine.h", "csrc/backend.h", "csrc/transport.h"]
 EXT_OUT = os.path.join(
     "torch_cgx_amd", "_C" + sysconfig.get_config_var("EXT_SUFFIX"))
 

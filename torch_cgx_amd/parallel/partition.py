@@ -1,6 +1,6 @@
 """Rank-chunk partitioning for the compressed allreduce.
 
-Python mirror of the C++ engine's partition (csrc/engine.cc), which itself
+Python mirror of the C++ engine's partition (csrc/plan.cc), which itself
 reproduces the semantics of the reference Quantizer::GetSizesAndOffsets
 (/root/reference/src/common/compressor.cc:265-299): a fused chunk of
 ``num_elements`` values spanning a list of layer slices is split into
