@@ -23,11 +23,6 @@ ncclRedOp_t to_nccl_op(const c10d::ReduceOp& op) {
   }
 }
 
-bool env_flag(const char* name) {
-  const char* v = std::getenv(name);
-  return v && *v && std::strcmp(v, "0") != 0;
-}
-
 void check_single(const std::vector<at::Tensor>& ts) {
   TORCH_CHECK(ts.size() == 1, "cgx: expected exactly one tensor per rank");
   // contiguity is only required on the RCCL/kernel path; the gloo CPU
@@ -95,7 +90,7 @@ bool WorkCGX::wait(std::chrono::milliseconds /*timeout*/) {
   if (recorded_) {
     auto cur = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(device_.index());
     CGX_HIP_CHECK(hipStreamWaitEvent(cur.stream(), ev_, 0));
-    if (env_flag("CGX_BLOCKING_WAIT")) CGX_HIP_CHECK(hipEventSynchronize(ev_));
+    if (env_blocking_wait()) CGX_HIP_CHECK(hipEventSynchronize(ev_));
   }
   return true;
 }
@@ -156,7 +151,9 @@ ProcessGroupCGX::ProcessGroupCGX(c10::intrusive_ptr<c10d::Store> store,
 ProcessGroupCGX::~ProcessGroupCGX() {
   // drain pending work before tearing communicators down
   if (stream_) (void)hipStreamSynchronize(stream_->stream());
-  for_each_engine_stream([](hipStream_t s) { (void)hipStreamSynchronize(s); });
+  if (reducer_)
+    reducer_->for_each_stream(
+        [](hipStream_t s) { (void)hipStreamSynchronize(s); });
   if (intra_comm_) (void)ncclCommDestroy(intra_comm_);
   if (cross_comm_) (void)ncclCommDestroy(cross_comm_);
   if (comm_) (void)ncclCommDestroy(comm_);
@@ -174,10 +171,11 @@ void ProcessGroupCGX::lazyInit(at::Device device) {
   device_index_ = device.index();
   c10::hip::HIPGuardMasqueradingAsCUDA guard(device_index_);
   comm_ = init_comm(*store_, "cgx/nccl_uid", size_, rank_);
-  tr_ = std::make_unique<RcclTransport>(comm_, rank_, size_);
+  tr_ = std::make_unique<RcclTransport>(comm_);
   stream_ = c10::hip::getStreamFromPoolMasqueradingAsCUDA(
       /*isHighPriority=*/true, device_index_);
-  engine_ = std::make_unique<Engine>(rank_, size_);
+  reducer_ = std::make_unique<Reducer>();
+  reducer_->flat.emplace(rank_, size_, tr_.get());
   CGX_HIP_CHECK(hipEventCreateWithFlags(&start_ev_, hipEventDisableTiming));
 
   // multi-node: build intra/cross communicators for the hierarchical path
@@ -186,34 +184,30 @@ void ProcessGroupCGX::lazyInit(at::Device device) {
   char host[256] = {0};
   gethostname(host, sizeof(host) - 1);
   topo_ = compute_topology(store_, rank_, size_, host);
-  const char* henv = std::getenv("CGX_HIERARCHICAL");
-  const bool want_hier = !(henv && std::strcmp(henv, "0") == 0);
   if (topo_.n_nodes > 1 && topo_.uniform && topo_.local_size > 1 &&
-      want_hier) {
+      env_hierarchical()) {
     // intra communicator: ranks on this node
     intra_comm_ =
         init_comm(*store_, "cgx/intra_uid/" + std::to_string(topo_.node_id),
                   topo_.local_size, topo_.local_rank);
-    intra_tr_ = std::make_unique<RcclTransport>(intra_comm_, topo_.local_rank,
-                                                topo_.local_size);
+    intra_tr_ = std::make_unique<RcclTransport>(intra_comm_);
     // cross communicator: peers with the same local_rank on every node
     cross_comm_ =
         init_comm(*store_, "cgx/cross_uid/" + std::to_string(topo_.local_rank),
                   topo_.n_nodes, topo_.node_id);
-    cross_tr_ = std::make_unique<RcclTransport>(cross_comm_, topo_.node_id,
-                                                topo_.n_nodes);
-    intra_engine_ = std::make_unique<Engine>(topo_.local_rank,
-                                             topo_.local_size);
-    cross_engine_ = std::make_unique<Engine>(topo_.node_id, topo_.n_nodes,
-                                             /*is_cross=*/true);
-    hierarchical_ = true;
+    cross_tr_ = std::make_unique<RcclTransport>(cross_comm_);
+    reducer_->intra.emplace(topo_.local_rank, topo_.local_size,
+                            intra_tr_.get());
+    reducer_->cross.emplace(topo_.node_id, topo_.n_nodes, cross_tr_.get(),
+                            /*is_cross=*/true);
+    reducer_->leader = topo_.local_rank == 0;
   }
-  if (env_flag("CGX_VERBOSE") && rank_ == 0) {
+  if (env_verbose() && rank_ == 0) {
     fprintf(stderr,
             "[cgx] init: world=%d nodes=%d local_size=%d hierarchical=%d "
             "device=%d\n",
-            size_, topo_.n_nodes, topo_.local_size, (int)hierarchical_,
-            device_index_);
+            size_, topo_.n_nodes, topo_.local_size,
+            (int)reducer_->hierarchical(), device_index_);
   }
 }
 
@@ -228,38 +222,69 @@ void check_async_error(ncclComm_t comm) {
 }
 }  // namespace
 
+// The one way onto the GPU: prologue, fn(stream_) -> completion stream,
+// epilogue.  The passthrough and compressed paths differ in the three places
+// marked below and nowhere else.
 template <typename Fn>
-c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::collective(
-    std::vector<at::Tensor> outputs, at::Device device, c10d::OpType op,
-    Fn&& fn) {
+c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::enqueue(
+    Path path, std::vector<at::Tensor> outputs, at::Device device,
+    c10d::OpType op, const char* title, Fn&& fn) {
   std::lock_guard<std::mutex> lock(mu_);
   lazyInit(device);
-  check_async_error(comm_);
+  for (ncclComm_t c : {comm_, intra_comm_, cross_comm_}) check_async_error(c);
   c10::hip::HIPGuardMasqueradingAsCUDA dguard(device_index_);
   auto cur = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(device_index_);
   CGX_HIP_CHECK(hipEventRecord(start_ev_, cur.stream()));
   CGX_HIP_CHECK(hipStreamWaitEvent(stream_->stream(), start_ev_, 0));
-  // RCCL forbids unordered concurrent ops on one communicator: fence this
-  // passthrough op behind any compressed-allreduce traffic still queued on
-  // the engine's comm/decode streams (the compressed path itself chains the
-  // other direction through start_ev_, so ordering is total).
-  for_each_engine_stream([&](hipStream_t s) {
-    CGX_HIP_CHECK(hipEventRecord(start_ev_, s));
-    CGX_HIP_CHECK(hipStreamWaitEvent(stream_->stream(), start_ev_, 0));
-  });
-  c10::hip::HIPStreamGuardMasqueradingAsCUDA sguard(stream_->unwrap());
-  fn(stream_->stream());
-  for (const auto& t : outputs) {
-    if (t.defined() && t.is_cuda()) {
-      c10::hip::HIPCachingAllocatorMasqueradingAsCUDA::
-          recordStreamMasqueradingAsCUDA(t.storage().data_ptr(), *stream_);
+  // (1) Passthrough waits on every engine stream: RCCL forbids unordered
+  // concurrent ops on one communicator, so it is fenced behind compressed
+  // traffic still queued there.  Compressed must NOT wait: that would
+  // serialise bucket N+1's quantize behind bucket N's traffic, the overlap
+  // the engine exists for (it orders the other direction by forking from
+  // stream_, so ordering is total).
+  if (path == Path::kPassthrough) {
+    reducer_->for_each_stream([&](hipStream_t s) {
+      CGX_HIP_CHECK(hipEventRecord(start_ev_, s));
+      CGX_HIP_CHECK(hipStreamWaitEvent(stream_->stream(), start_ev_, 0));
+    });
+  }
+  // (2) The Work ends on the stream fn returns, current for recordEnd so the
+  // future chains callbacks there: stream_ for passthrough, the reducer's
+  // last stream for compressed.
+  auto fin = c10::hip::getStreamFromExternalMasqueradingAsCUDA(
+      fn(stream_->stream()), device_index_);
+  c10::hip::HIPStreamGuardMasqueradingAsCUDA sguard(fin.unwrap());
+  auto keep_alive_on = [&](const c10::hip::HIPStreamMasqueradingAsCUDA& s) {
+    for (const auto& t : outputs) {
+      if (t.defined() && t.is_cuda()) {
+        c10::hip::HIPCachingAllocatorMasqueradingAsCUDA::
+            recordStreamMasqueradingAsCUDA(t.storage().data_ptr(), s);
+      }
     }
+  };
+  keep_alive_on(*stream_);
+  // (3) Compressed outputs are also touched by every engine stream.
+  if (path == Path::kCompressed) {
+    reducer_->for_each_stream([&](hipStream_t s) {
+      keep_alive_on(c10::hip::getStreamFromExternalMasqueradingAsCUDA(
+          s, device_index_));
+    });
   }
   auto work = c10::make_intrusive<WorkCGX>(rank_, op, device,
-                                           std::move(outputs),
-                                           c10d::opTypeToString(op).c_str());
-  work->recordEnd(*stream_);
+                                           std::move(outputs), title);
+  work->recordEnd(fin);
   return work;
+}
+
+template <typename Fn>
+c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::collective(
+    std::vector<at::Tensor> outputs, at::Device device, c10d::OpType op,
+    Fn&& fn) {
+  return enqueue(Path::kPassthrough, std::move(outputs), device, op,
+                 c10d::opTypeToString(op).c_str(), [&](hipStream_t s) {
+                   fn(s);
+                   return s;
+                 });
 }
 
 c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::allreduce(
@@ -269,67 +294,13 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::allreduce(
   if (!t.is_cuda()) {
     return cpu_delegate().allreduce(tensors, opts);
   }
-  const bool compressible =
-      opts.reduceOp == c10d::ReduceOp::SUM &&
-      (t.scalar_type() == at::kFloat || t.scalar_type() == at::kHalf ||
-       t.scalar_type() == at::kBFloat16);
   auto op = opts.reduceOp;
-  if (compressible) {
-    // pipelined path: engine fans work over quantize/comm/deq streams and
-    // returns the stream carrying the final op; the Work's end event and
-    // future live there so the NEXT bucket's quantize can overlap this
-    // bucket's xGMI traffic.
-    std::lock_guard<std::mutex> lock(mu_);
-    lazyInit(t.device());
-    check_async_error(comm_);
-    if (hierarchical_) {
-      check_async_error(intra_comm_);
-      check_async_error(cross_comm_);
-    }
-    c10::hip::HIPGuardMasqueradingAsCUDA dguard(device_index_);
-    auto cur = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(device_index_);
-    CGX_HIP_CHECK(hipEventRecord(start_ev_, cur.stream()));
-    CGX_HIP_CHECK(hipStreamWaitEvent(stream_->stream(), start_ev_, 0));
-    hipStream_t fin = stream_->stream();
-    if (size_ > 1) {
-      const char* ib = std::getenv("CGX_INTRA_BROADCAST");
-      const bool hier = hierarchical_ && !(ib && std::strcmp(ib, "0") == 0);
-      if (hier) {
-        // intra-node compressed allreduce over xGMI, cross-node reduction on
-        // node leaders, then intra broadcast of the result.  The layer
-        // registry is consulted exactly ONCE per bucket so the cursor stays
-        // in lockstep on every rank (leaders run two engine passes).
-        cgx::Registry::BucketInfo info;
-        const bool matched =
-            cgx::Registry::get().next(t.numel(), t.data_ptr(), &info);
-        fin = intra_engine_->allreduce(t, intra_tr_.get(),
-                                       stream_->stream(), &info, matched);
-        if (topo_.local_rank == 0)
-          fin = cross_engine_->allreduce(t, cross_tr_.get(), fin, &info,
-                                         matched);
-        fin = intra_engine_->broadcast(t, /*root=*/0, intra_tr_.get(), fin);
-      } else {
-        fin = engine_->allreduce(t, tr_.get(), stream_->stream());
-      }
-    }
-    auto fin_masq = c10::hip::getStreamFromExternalMasqueradingAsCUDA(
-        fin, device_index_);
-    c10::hip::HIPStreamGuardMasqueradingAsCUDA sguard(fin_masq.unwrap());
-    auto touch = [&](hipStream_t s) {
-      if (!s) return;
-      c10::hip::HIPCachingAllocatorMasqueradingAsCUDA::
-          recordStreamMasqueradingAsCUDA(
-              t.storage().data_ptr(),
-              c10::hip::getStreamFromExternalMasqueradingAsCUDA(
-                  s, device_index_));
-    };
-    touch(stream_->stream());
-    for_each_engine_stream(touch);
-    auto work = c10::make_intrusive<WorkCGX>(rank_, c10d::OpType::ALLREDUCE,
-                                             t.device(), tensors,
-                                             "cgx:allreduce_compressed");
-    work->recordEnd(fin_masq);
-    return work;
+  if (op == c10d::ReduceOp::SUM && is_compressible(t.scalar_type())) {
+    // pipelined path: the reducer fans work over quantize/comm/deq streams
+    // and returns the stream carrying the final op
+    return enqueue(Path::kCompressed, tensors, t.device(),
+                   c10d::OpType::ALLREDUCE, "cgx:allreduce_compressed",
+                   [&](hipStream_t s) { return reducer_->allreduce(t, s); });
   }
   return collective(tensors, t.device(), c10d::OpType::ALLREDUCE,
                     [this, t, op](hipStream_t s) {
@@ -658,7 +629,6 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::alltoall(
                     });
 }
 
-namespace {
 // CGX_P2P_ANYSOURCE=1 enables MPI_ANY_SOURCE-style GPU receives (reference
 // ProcessGroupCGX.cc:765-785): RCCL p2p needs a known peer, so every GPU
 // send also posts a tiny gloo "announcement" carrying the source rank, and
@@ -666,12 +636,6 @@ namespace {
 // its peer from it).  Off by default — it adds a host-side gloo message to
 // every GPU send, and mixing announced and plain p2p would desynchronize
 // the pairing, so the flag must be set consistently on ALL ranks.
-bool p2p_anysource() {
-  static const bool v = env_flag("CGX_P2P_ANYSOURCE");
-  return v;
-}
-}  // namespace
-
 c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::send(
     std::vector<at::Tensor>& tensors, int dstRank, int tag) {
   check_single(tensors);
@@ -679,7 +643,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::send(
   if (!t.is_cuda()) {
     return cpu_delegate().send(tensors, dstRank, tag);
   }
-  if (p2p_anysource()) {
+  if (env_p2p_anysource()) {
     TORCH_CHECK(cpu_, "cgx: CGX_P2P_ANYSOURCE requires the CPU delegate");
     std::vector<at::Tensor> ann{
         at::full({1}, rank_, at::TensorOptions().dtype(at::kInt))};
@@ -709,7 +673,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::recv(
   if (!t.is_cuda()) {
     return cpu_delegate().recv(tensors, srcRank, tag);
   }
-  if (p2p_anysource()) {
+  if (env_p2p_anysource()) {
     // consume this sender's announcement to keep the pairing in lockstep
     std::vector<at::Tensor> ann{
         at::zeros({1}, at::TensorOptions().dtype(at::kInt))};
@@ -729,7 +693,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::recvAnysource(
   if (!tensors[0].is_cuda()) {
     return cpu_delegate().recvAnysource(tensors, tag);
   }
-  TORCH_CHECK(p2p_anysource(),
+  TORCH_CHECK(env_p2p_anysource(),
               "cgx: recvAnysource for GPU tensors requires "
               "CGX_P2P_ANYSOURCE=1 on every rank (RCCL p2p needs a known "
               "source; the flag adds a gloo source announcement to each "
@@ -760,7 +724,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::barrier(
   if (comm_) {
     std::lock_guard<std::mutex> lock(mu_);
     CGX_HIP_CHECK(hipStreamSynchronize(stream_->stream()));
-    for_each_engine_stream(
+    reducer_->for_each_stream(
         [](hipStream_t s) { CGX_HIP_CHECK(hipStreamSynchronize(s)); });
   }
   if (cpu_) {

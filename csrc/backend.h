@@ -27,7 +27,7 @@
 #include <optional>
 #include <vector>
 
-#include "engine.h"
+#include "reducer.h"
 
 namespace cgx {
 
@@ -131,23 +131,25 @@ class ProcessGroupCGX : public c10d::Backend {
  private:
   void lazyInit(at::Device device);
 
-  // Enqueue fn(side_stream) chained after the current stream; returns the
-  // event-backed Work.  Caller holds no lock.
+  // Prologue and epilogue of every GPU collective (under mu_): lazyInit,
+  // async-error check of every live communicator, fork stream_ behind the
+  // caller's current stream, fn(stream_) -> the stream the op completes on,
+  // then keep `outputs` alive on the streams that touch them and return the
+  // Work whose end event sits on that stream.  `path` selects the
+  // passthrough/compressed differences; see the definition.
+  enum class Path { kPassthrough, kCompressed };
+  template <typename Fn>
+  c10::intrusive_ptr<c10d::Work> enqueue(Path path,
+                                         std::vector<at::Tensor> outputs,
+                                         at::Device device, c10d::OpType op,
+                                         const char* title, Fn&& fn);
+
+  // RCCL passthrough: enqueue fn(stream_) behind the current stream and all
+  // engine traffic; returns the event-backed Work.  Caller holds no lock.
   template <typename Fn>
   c10::intrusive_ptr<c10d::Work> collective(std::vector<at::Tensor> outputs,
                                             at::Device device,
                                             c10d::OpType op, Fn&& fn);
-
-  // fn(stream) for the comm and deq stream of every live engine
-  template <typename Fn>
-  void for_each_engine_stream(Fn&& fn) const {
-    for (Engine* e : {engine_.get(), intra_engine_.get(),
-                      cross_engine_.get()}) {
-      if (!e) continue;
-      fn(e->comm_stream());
-      fn(e->deq_stream());
-    }
-  }
 
   // the CPU (gloo) delegate; CPU tensors cannot be served without one
   c10d::Backend& cpu_delegate() const {
@@ -157,24 +159,19 @@ class ProcessGroupCGX : public c10d::Backend {
 
   c10::intrusive_ptr<c10d::Store> store_;
   c10::intrusive_ptr<c10d::Backend> cpu_;
-  ncclComm_t comm_ = nullptr;
-  std::unique_ptr<RcclTransport> tr_;
   // CGX_P2P_ANYSOURCE: in-flight gloo source announcements (fire-and-forget)
   std::mutex ann_mu_;
   std::deque<c10::intrusive_ptr<c10d::Work>> pending_ann_;
   int device_index_ = -1;
-  std::unique_ptr<Engine> engine_;
-  // hierarchical (multi-node) mode: intra-node SRA + cross-node reduction on
-  // node leaders + intra broadcast (reference CGX_INTRA_BROADCAST semantics,
-  // mpi_allreduce_operations.cc:160-183); single-node -> flat path.
+  // Communicators (created in lazyInit, destroyed here) and the transports
+  // over them.  intra/cross exist in hierarchical (multi-node) mode only.
   Topology topo_;
+  ncclComm_t comm_ = nullptr;
   ncclComm_t intra_comm_ = nullptr;
   ncclComm_t cross_comm_ = nullptr;
-  std::unique_ptr<RcclTransport> intra_tr_;
-  std::unique_ptr<RcclTransport> cross_tr_;
-  std::unique_ptr<Engine> intra_engine_;
-  std::unique_ptr<Engine> cross_engine_;
-  bool hierarchical_ = false;
+  std::unique_ptr<RcclTransport> tr_, intra_tr_, cross_tr_;
+  // the compression engines over those transports, filled by lazyInit
+  std::unique_ptr<Reducer> reducer_;
   std::optional<c10::hip::HIPStreamMasqueradingAsCUDA> stream_;
   hipEvent_t start_ev_ = nullptr;
   std::mutex mu_;

@@ -19,8 +19,7 @@
 #include <tuple>
 
 #include "backend.h"
-#include "engine.h"
-#include "transport.h"
+#include "reducer.h"
 
 namespace cgx {
 namespace {
@@ -59,18 +58,65 @@ void run_rank_threads(int ws, int dev,
     if (errs[r]) std::rethrow_exception(errs[r]);
 }
 
-// Drive the REAL engine code at world size ws on ONE GPU: `buckets[r]` is
-// rank r's flat bucket; ws Engine instances (each with its own streams,
-// staging and events — exactly the production objects) exchange compressed
-// chunks through the loopback transport (device-to-device copies with full
-// stream/event fencing).  This is the hardware test seam the multi-rank
-// SRA/Ring path runs under `pytest -m gpu` with a single MI355X: RCCL
+// N ranks inside one process: a Reducer per rank over loopback transports
+// (device-to-device copies with full stream/event fencing) -- the production
+// engines with their own streams, staging and events, composed by the
+// production Reducer.  local_size == 0 builds the flat stage only (one world
+// hub); otherwise ws = n_nodes * local_size and every rank also gets an intra
+// stage on its node's hub, each node leader a cross stage on the leaders'
+// hub, like the backend's lazyInit.
+struct LoopbackWorld {
+  std::vector<std::unique_ptr<LoopbackHub>> hubs;
+  std::vector<std::unique_ptr<LoopbackTransport>> trs;
+  std::vector<Reducer> ranks;
+
+  LoopbackWorld(int ws, int local_size) {
+    ranks.resize(ws);
+    LoopbackHub* world = hub(ws);
+    for (int r = 0; r < ws; r++) ranks[r].flat.emplace(r, ws, tr(world, r));
+    if (local_size == 0) return;
+    const int nodes = ws / local_size;
+    LoopbackHub* cross = hub(nodes);
+    for (int nd = 0; nd < nodes; nd++) {
+      LoopbackHub* intra = hub(local_size);
+      for (int lr = 0; lr < local_size; lr++) {
+        Reducer& red = ranks[nd * local_size + lr];
+        red.intra.emplace(lr, local_size, tr(intra, lr));
+        red.leader = lr == 0;
+        if (red.leader)
+          red.cross.emplace(nd, nodes, tr(cross, nd), /*is_cross=*/true);
+      }
+    }
+  }
+  // poison every hub so no peer of a failed rank blocks
+  void abort() {
+    for (auto& h : hubs) h->abort();
+  }
+
+ private:
+  LoopbackHub* hub(int world) {
+    hubs.push_back(std::make_unique<LoopbackHub>(world));
+    return hubs.back().get();
+  }
+  Transport* tr(LoopbackHub* h, int rank) {
+    trs.push_back(std::make_unique<LoopbackTransport>(h, rank));
+    return trs.back().get();
+  }
+};
+
+// Run body(rank's Reducer, quantize stream, rank) -> completion stream on one
+// thread per rank of a LoopbackWorld over `tensors` (tensors[r] is rank r's),
+// then drain every stream the rank used.  This is the hardware test seam the
+// multi-rank paths run under `pytest -m gpu` with a single MI355X: RCCL
 // itself refuses two ranks on one device.
-void run_loopback(const std::vector<at::Tensor>& tensors,
-                  const std::function<hipStream_t(Engine&, Transport*,
-                                                  hipStream_t, int)>& body) {
+void run_loopback(
+    const std::vector<at::Tensor>& tensors, int local_size,
+    const std::function<hipStream_t(Reducer&, hipStream_t, int)>& body) {
   const int ws = (int)tensors.size();
   TORCH_CHECK(ws >= 2, "loopback: need >= 2 per-rank tensors");
+  TORCH_CHECK(local_size == 0 || (ws % local_size == 0 && ws / local_size >= 2),
+              "loopback: hierarchical world must be n_nodes*local_size with "
+              ">= 2 nodes");
   for (const auto& t : tensors) {
     TORCH_CHECK(t.is_cuda() && t.is_contiguous(),
                 "loopback: CUDA contiguous tensors required");
@@ -81,34 +127,34 @@ void run_loopback(const std::vector<at::Tensor>& tensors,
   }
   const int dev = tensors[0].device().index();
   c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-  LoopbackHub hub(ws);
-  std::vector<std::unique_ptr<Engine>> engines;
-  std::vector<std::unique_ptr<LoopbackTransport>> trs;
-  for (int r = 0; r < ws; r++) {
-    engines.push_back(std::make_unique<Engine>(r, ws));
-    trs.push_back(std::make_unique<LoopbackTransport>(&hub, r));
-  }
+  LoopbackWorld world(ws, local_size);
   run_rank_threads(
       ws, dev,
       [&](int r, hipStream_t qs) {
-        hipStream_t fin = body(*engines[r], trs[r].get(), qs, r);
+        hipStream_t fin = body(world.ranks[r], qs, r);
         CGX_HIP_CHECK(hipStreamSynchronize(fin));
         CGX_HIP_CHECK(hipStreamSynchronize(qs));
-        CGX_HIP_CHECK(hipStreamSynchronize(engines[r]->comm_stream()));
-        CGX_HIP_CHECK(hipStreamSynchronize(engines[r]->deq_stream()));
+        world.ranks[r].for_each_stream(
+            [](hipStream_t s) { CGX_HIP_CHECK(hipStreamSynchronize(s)); });
       },
-      [&] { hub.abort(); });
+      [&] { world.abort(); });
 }
 
-void py_loopback_allreduce(std::vector<at::Tensor> buckets) {
-  const int64_t numel = buckets.empty() ? 0 : buckets[0].numel();
-  // resolve the registry ONCE and force it into every engine, exactly like
-  // the hierarchical path (one cursor step per bucket across all ranks)
+// The rank threads share one layer registry, so the harness takes its one
+// cursor step per bucket up front and forces the result into every rank.
+struct Resolved {
+  explicit Resolved(int64_t numel)
+      : matched(Registry::get().next(numel, nullptr, &info)) {}
   Registry::BucketInfo info;
-  const bool matched = Registry::get().next(numel, nullptr, &info);
-  run_loopback(buckets, [&](Engine& e, Transport* tr, hipStream_t qs, int r) {
-    return e.allreduce(buckets[r], tr, qs, &info, matched);
-  });
+  bool matched;
+};
+
+void py_loopback_allreduce(std::vector<at::Tensor> buckets) {
+  const Resolved reg(buckets.empty() ? 0 : buckets[0].numel());
+  run_loopback(buckets, /*local_size=*/0,
+               [&](Reducer& red, hipStream_t qs, int r) {
+                 return red.allreduce(buckets[r], qs, &reg.info, reg.matched);
+               });
 }
 
 // Multiple allreduce steps on PERSISTENT engines (one set of engines for
@@ -124,87 +170,35 @@ void py_loopback_allreduce_multi(
     TORCH_CHECK((int)st.size() == ws && st[0].numel() == numel,
                 "loopback_allreduce_multi: ragged steps");
   }
-  Registry::BucketInfo info;
-  const bool matched = Registry::get().next(numel, nullptr, &info);
-  run_loopback(steps[0],
-               [&](Engine& e, Transport* tr, hipStream_t qs, int r) {
+  const Resolved reg(numel);
+  run_loopback(steps[0], /*local_size=*/0,
+               [&](Reducer& red, hipStream_t qs, int r) {
                  hipStream_t fin = qs;
-                 for (size_t s = 0; s < steps.size(); s++) {
-                   fin = e.allreduce(steps[s][r], tr, qs, &info, matched);
-                 }
+                 for (auto& st : steps)
+                   fin = red.allreduce(st[r], qs, &reg.info, reg.matched);
                  return fin;
                });
 }
 
 void py_loopback_broadcast(std::vector<at::Tensor> tensors, int64_t root) {
-  run_loopback(tensors, [&](Engine& e, Transport* tr, hipStream_t qs, int r) {
-    return e.broadcast(tensors[r], (int)root, tr, qs);
-  });
+  run_loopback(tensors, /*local_size=*/0,
+               [&](Reducer& red, hipStream_t qs, int r) {
+                 return red.flat->engine->broadcast(tensors[r], (int)root,
+                                                    red.flat->tr, qs);
+               });
 }
 
-// Hierarchical flow on one GPU (backend.cc ProcessGroupCGX::allreduce
-// `hier` branch): ws = n_nodes * local_size ranks; each "node" gets an
-// intra hub, the node leaders share a cross hub.  Per rank: intra-node
-// compressed allreduce, cross-node reduction on the leader, intra
-// broadcast of the result — the registry resolved ONCE for all engines.
+// The multi-node allreduce on one GPU: ws = n_nodes * local_size ranks run
+// Reducer::allreduce, the call ProcessGroupCGX makes per bucket -- the
+// hierarchical flow, or the flat one under CGX_INTRA_BROADCAST=0.
 void py_loopback_hierarchical(std::vector<at::Tensor> buckets,
                               int64_t local_size) {
-  const int ws = (int)buckets.size();
-  TORCH_CHECK(local_size >= 1 && ws % local_size == 0 && ws >= 2,
-              "loopback_hierarchical: world must be n_nodes*local_size");
-  const int nodes = ws / (int)local_size;
-  TORCH_CHECK(nodes >= 2, "loopback_hierarchical: need >= 2 nodes");
-  for (const auto& t : buckets) {
-    TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
-                    t.numel() == buckets[0].numel() &&
-                    t.device() == buckets[0].device(),
-                "loopback_hierarchical: matching CUDA tensors required");
-  }
-  const int dev = buckets[0].device().index();
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-  Registry::BucketInfo info;
-  const bool matched =
-      Registry::get().next(buckets[0].numel(), nullptr, &info);
-  std::vector<std::unique_ptr<LoopbackHub>> intra_hubs;
-  for (int nd = 0; nd < nodes; nd++)
-    intra_hubs.push_back(std::make_unique<LoopbackHub>((int)local_size));
-  LoopbackHub cross_hub(nodes);
-  std::vector<std::unique_ptr<Engine>> intra_eng;    // per rank
-  std::vector<std::unique_ptr<LoopbackTransport>> intra_tr;
-  std::vector<std::unique_ptr<Engine>> cross_eng;    // per node (leader)
-  std::vector<std::unique_ptr<LoopbackTransport>> cross_tr;
-  for (int r = 0; r < ws; r++) {
-    const int nd = r / (int)local_size;
-    const int lr = r % (int)local_size;
-    intra_eng.push_back(std::make_unique<Engine>(lr, (int)local_size));
-    intra_tr.push_back(
-        std::make_unique<LoopbackTransport>(intra_hubs[nd].get(), lr));
-  }
-  for (int nd = 0; nd < nodes; nd++) {
-    cross_eng.push_back(
-        std::make_unique<Engine>(nd, nodes, /*is_cross=*/true));
-    cross_tr.push_back(std::make_unique<LoopbackTransport>(&cross_hub, nd));
-  }
-  run_rank_threads(
-      ws, dev,
-      [&](int r, hipStream_t qs) {
-        const int nd = r / (int)local_size;
-        const int lr = r % (int)local_size;
-        hipStream_t fin = intra_eng[r]->allreduce(
-            buckets[r], intra_tr[r].get(), qs, &info, matched);
-        if (lr == 0) {
-          fin = cross_eng[nd]->allreduce(buckets[r], cross_tr[nd].get(), fin,
-                                         &info, matched);
-        }
-        fin = intra_eng[r]->broadcast(buckets[r], /*root=*/0,
-                                      intra_tr[r].get(), fin);
-        CGX_HIP_CHECK(hipStreamSynchronize(fin));
-        CGX_HIP_CHECK(hipStreamSynchronize(qs));
-      },
-      [&] {
-        for (auto& h : intra_hubs) h->abort();
-        cross_hub.abort();
-      });
+  TORCH_CHECK(local_size >= 1, "loopback_hierarchical: local_size >= 1");
+  const Resolved reg(buckets.empty() ? 0 : buckets[0].numel());
+  run_loopback(buckets, (int)local_size,
+               [&](Reducer& red, hipStream_t qs, int r) {
+                 return red.allreduce(buckets[r], qs, &reg.info, reg.matched);
+               });
 }
 
 // Copy a routed group's descs (followed by cum, if any) to the device.
@@ -508,13 +502,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     d["skip_incomplete"] = c.skip_incomplete;
     d["dummy"] = c.dummy;
     d["intra_compress"] = c.intra_compress;
+    d["intra_broadcast"] = c.intra_broadcast;
     d["error_feedback"] = c.error_feedback;
     return d;
   });
+  m.def("env_flag", &cgx::env_flag, py::arg("name"),
+        py::arg("default") = false,
+        "Test seam: the textual boolean parser (only \"0\" is false).");
+  m.def("env_int", &cgx::env_int, py::arg("name"), py::arg("default"),
+        "Test seam: the numeric parser behind the `!= 0` booleans.");
   m.def("loopback_allreduce", &cgx::py_loopback_allreduce, py::arg("buckets"),
-        "Run the production Engine::allreduce at world_size=len(buckets) on "
-        "one GPU via the loopback transport; buckets[r] is rank r's flat "
-        "bucket tensor, reduced in place.");
+        "Run Reducer::allreduce (flat) at world_size=len(buckets) on one GPU "
+        "via the loopback transport; buckets[r] is rank r's flat bucket "
+        "tensor, reduced in place.");
   m.def("loopback_broadcast", &cgx::py_loopback_broadcast, py::arg("tensors"),
         py::arg("root") = 0,
         "Run the production Engine::broadcast at world_size=len(tensors) on "
@@ -526,9 +526,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "carry across steps.");
   m.def("loopback_hierarchical", &cgx::py_loopback_hierarchical,
         py::arg("buckets"), py::arg("local_size"),
-        "Run the production hierarchical flow (intra allreduce -> leader "
-        "cross reduction -> intra broadcast) for n_nodes*local_size ranks "
-        "on one GPU via loopback transports.");
+        "Run Reducer::allreduce, the backend's per-bucket call, for "
+        "n_nodes*local_size ranks on one GPU via loopback transports: intra "
+        "allreduce -> leader cross reduction -> intra broadcast, or the "
+        "flat path under CGX_INTRA_BROADCAST=0.");
   m.def("quantize", &cgx::py_quantize, py::arg("x"), py::arg("bits"),
         py::arg("bucket_size"), py::arg("stochastic") = false,
         py::arg("seed") = 0, py::arg("skip_incomplete") = false,

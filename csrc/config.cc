@@ -12,6 +12,34 @@ int64_t env_int(const char* name, int64_t dflt) {
   return std::atoll(v);
 }
 
+bool env_flag(const char* name, bool dflt) {
+  const char* v = std::getenv(name);
+  if (!v || !*v) return dflt;
+  return std::strcmp(v, "0") != 0;
+}
+
+bool env_hierarchical() { return env_flag("CGX_HIERARCHICAL", true); }
+bool env_verbose() { return env_flag("CGX_VERBOSE"); }
+bool env_blocking_wait() { return env_flag("CGX_BLOCKING_WAIT"); }
+
+bool env_p2p_anysource() {
+  static const bool v = env_flag("CGX_P2P_ANYSOURCE");
+  return v;
+}
+
+bool env_timings() {
+  static const bool v = env_int("CGX_TIMINGS", 0) != 0;
+  return v;
+}
+
+int env_max_blocks() {
+  static const int v = [] {
+    const int x = (int)env_int("CGX_MAX_BLOCKS", 0);
+    return x > 0 ? x : 0;
+  }();
+  return v;
+}
+
 EngineConfig EngineConfig::from_env() {
   EngineConfig c;
   c.fusion_bytes = env_int("CGX_FUSION_BUFFER_SIZE_MB", 64) << 20;
@@ -24,6 +52,7 @@ EngineConfig EngineConfig::from_env() {
       env_int("CGX_COMPRESSION_SKIP_INCOMPLETE_BUCKETS", 0) != 0;
   c.dummy = env_int("CGX_DEBUG_DUMMY_COMPRESSION", 0) != 0;
   c.intra_compress = env_int("CGX_INTRA_COMPRESS", 1) != 0;
+  c.intra_broadcast = env_flag("CGX_INTRA_BROADCAST", true);
   c.error_feedback = env_int("CGX_ERROR_FEEDBACK", 0) != 0;
   c.debug_a2a = env_int("CGX_DEBUG_ALL_TO_ALL_REDUCTION", 0) != 0;
   const char* fr = std::getenv("CGX_COMPRESSION_FAKE_RATIO");

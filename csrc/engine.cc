@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cstring>
 #include <initializer_list>
+#include <optional>
 
 namespace cgx {
 
@@ -52,14 +53,24 @@ void* DescRing::commit(size_t bytes, hipStream_t stream) {
 // ---------------------------------------------------------------------------
 // dtype maps
 // ---------------------------------------------------------------------------
-DType dtype_of(at::ScalarType st) {
+// the one list of dtypes the kernels compress
+static std::optional<DType> compressed_dtype(at::ScalarType st) {
   switch (st) {
     case at::kFloat: return DType::F32;
     case at::kHalf: return DType::F16;
     case at::kBFloat16: return DType::BF16;
-    default:
-      TORCH_CHECK(false, "cgx: unsupported compression dtype ", st);
+    default: return std::nullopt;
   }
+}
+
+bool is_compressible(at::ScalarType st) {
+  return compressed_dtype(st).has_value();
+}
+
+DType dtype_of(at::ScalarType st) {
+  const auto dt = compressed_dtype(st);
+  TORCH_CHECK(dt, "cgx: unsupported compression dtype ", st);
+  return *dt;
 }
 
 DType dtype_of(const at::Tensor& t) { return dtype_of(t.scalar_type()); }
@@ -448,9 +459,7 @@ hipStream_t Engine::broadcast(at::Tensor t, int root, Transport* tr,
   const int64_t n = t.numel();
   const bool compress = !cfg.dummy && cfg.intra_compress &&
                         cfg.default_bits <= 8 && n > cfg.min_elems &&
-                        (t.scalar_type() == at::kFloat ||
-                         t.scalar_type() == at::kHalf ||
-                         t.scalar_type() == at::kBFloat16);
+                        is_compressible(t.scalar_type());
   if (!compress || size_ <= 1) {
     if (size_ > 1) {
       tr->broadcast(t.data_ptr(), n, (int)t.element_size(), nccl_dtype(t),
@@ -519,7 +528,6 @@ hipStream_t Engine::allreduce(at::Tensor bucket, Transport* tr,
     tr->allreduce_sum_group(bufs, ndt, comm_stream_);
   }
 
-  static const bool timings_on = env_int("CGX_TIMINGS", 0) != 0;
   for (size_t ci = 0; ci < bp.chunks.size(); ci++) {
     const std::vector<LayerView>& vs = bp.chunks[ci];
     // error-feedback residual identity for this (bucket, chunk): registry
@@ -528,7 +536,7 @@ hipStream_t Engine::allreduce(at::Tensor bucket, Transport* tr,
     const int64_t fb_key =
         matched ? (((int64_t)info.idx << 20) | (int64_t)ci)
                 : -(int64_t)(reinterpret_cast<uintptr_t>(vs[0].data) >> 3);
-    timer_.begin(qs, timings_on && !cfg.ring);
+    timer_.begin(qs, env_timings() && !cfg.ring);
     if (cfg.debug_a2a) {
       a2a_chunk(vs, dt, tr, qs, cfg);
     } else if (cfg.ring && size_ > 2) {

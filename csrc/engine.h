@@ -159,6 +159,8 @@ class Engine {
   uint64_t seed_;
 };
 
+// fp32/fp16/bf16: the dtypes the kernels compress (dtype_of throws on others)
+bool is_compressible(at::ScalarType st);
 DType dtype_of(at::ScalarType st);
 DType dtype_of(const at::Tensor& t);
 at::ScalarType scalar_type_of(DType dt);

@@ -42,10 +42,10 @@
 
 #include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #include "compress.h"
+#include "config.h"
 
 namespace cgx {
 namespace {
@@ -1554,12 +1554,8 @@ __global__ __launch_bounds__(kThreads) void k_add(const T* __restrict__ x,
 inline int max_blocks() {
   // CGX_MAX_BLOCKS: experimentation knob for grid-size sweeps (default
   // kMaxBlocks = 4096, i.e. 2 resident workgroup generations on 256 CUs)
-  static const int v = [] {
-    const char* e = std::getenv("CGX_MAX_BLOCKS");
-    const int x = e && *e ? std::atoi(e) : 0;
-    return x > 0 ? x : kMaxBlocks;
-  }();
-  return v;
+  const int x = env_max_blocks();
+  return x > 0 ? x : kMaxBlocks;
 }
 
 inline int grid_for(int64_t work, int per_block) {

@@ -56,10 +56,7 @@ struct Transport {
 
 class RcclTransport final : public Transport {
  public:
-  RcclTransport(ncclComm_t comm, int rank, int size) : comm_(comm) {
-    (void)rank;
-    (void)size;
-  }
+  explicit RcclTransport(ncclComm_t comm) : comm_(comm) {}
   void exchange(const std::vector<Op>& sends, const std::vector<Op>& recvs,
                 hipStream_t stream) override;
   void broadcast(void* ptr, int64_t count, int esize, ncclDataType_t dt,

@@ -23,7 +23,10 @@ REDUCTION_VARS = ("CGX_REDUCTION_TYPE", "CGX_INNER_REDUCTION_TYPE",
 def _clean_env():
     saved = {k: os.environ.pop(k, None)
              for k in REDUCTION_VARS + ("CGX_DEBUG_ALL_TO_ALL_REDUCTION",
-                                        "CGX_ERROR_FEEDBACK")}
+                                        "CGX_ERROR_FEEDBACK",
+                                        "CGX_INTRA_BROADCAST",
+                                        "CGX_STOCHASTIC_ROUNDING",
+                                        "CGX_VERBOSE")}
     yield
     for k, v in saved.items():
         if v is None:
@@ -65,6 +68,39 @@ def test_debug_a2a_flag():
     assert _C.parse_engine_config()["debug_a2a"] is False
     os.environ["CGX_DEBUG_ALL_TO_ALL_REDUCTION"] = "1"
     assert _C.parse_engine_config()["debug_a2a"] is True
+
+
+@pytest.mark.parametrize("value,expected", [(None, True), ("0", False),
+                                            ("1", True), ("", True)])
+def test_intra_broadcast_flag(value, expected):
+    """CGX_INTRA_BROADCAST defaults to on; only the literal "0" turns the
+    hierarchical flow off (the reducer re-reads it every bucket)."""
+    if value is not None:
+        os.environ["CGX_INTRA_BROADCAST"] = value
+    assert _C.parse_engine_config()["intra_broadcast"] is expected
+
+
+def test_boolean_parsers_differ():
+    """Two boolean conventions coexist, per variable: env_flag variables are
+    true for anything but "0"; `env_int != 0` variables parse a number, so a
+    non-numeric value is false."""
+    os.environ["CGX_INTRA_BROADCAST"] = "yes"    # env_flag, default on
+    os.environ["CGX_STOCHASTIC_ROUNDING"] = "yes"  # env_int, default on
+    cfg = _C.parse_engine_config()
+    assert cfg["intra_broadcast"] is True
+    assert cfg["stochastic"] is False
+    # the parsers themselves, on a default-off flag
+    assert _C.env_flag("CGX_VERBOSE") is False
+    assert _C.env_flag("CGX_VERBOSE", True) is True
+    os.environ["CGX_VERBOSE"] = "yes"
+    assert _C.env_flag("CGX_VERBOSE") is True
+    assert _C.env_int("CGX_VERBOSE", 0) == 0
+    os.environ["CGX_VERBOSE"] = "0"
+    assert _C.env_flag("CGX_VERBOSE", True) is False
+    os.environ["CGX_VERBOSE"] = ""
+    assert _C.env_flag("CGX_VERBOSE") is False
+    assert _C.env_flag("CGX_VERBOSE", True) is True
+    assert _C.env_int("CGX_VERBOSE", 7) == 7
 
 
 def test_registry_pointer_binding_disambiguates_equal_totals():

@@ -33,6 +33,7 @@ ENV_KEYS = (
     "CGX_CROSS_REDUCTION_TYPE", "CGX_REDUCTION_TYPE",
     "CGX_FUSION_BUFFER_SIZE_MB", "CGX_DEBUG_ALL_TO_ALL_REDUCTION",
     "CGX_ERROR_FEEDBACK", "CGX_COMPRESSION_MINIMAL_SIZE",
+    "CGX_INTRA_BROADCAST",
 )
 
 
@@ -275,13 +276,32 @@ def test_compressed_broadcast(_env, ws):
         assert torch.equal(tensors[r].cpu(), expected), r
 
 
+def _composed_hier_sim(cpu, nodes, local, bits, bucket):
+    """CPU expectation of the hierarchical flow: per-node SRA, then cross
+    reduction over the node results (SRA at 2 nodes -- the engine's ring
+    needs >2 -- else Ring, the cross default), then the broadcast quantize
+    round trip of the leader's result."""
+    n = cpu[0].numel()
+    node_res = []
+    for nd in range(nodes):
+        r = sra_sim.sra_allreduce(
+            [cpu[nd * local + k].clone() for k in range(local)],
+            [n], [(bits, bucket)])
+        node_res.append(r[0])
+    reduce = sra_sim.ring_allreduce if nodes > 2 else sra_sim.sra_allreduce
+    cross = reduce([t.clone() for t in node_res], [n], [(bits, bucket)])
+    return golden.dequantize(
+        golden.quantize(cross[0], bits, bucket, rand=0.5), n, torch.float32,
+        bits, bucket)
+
+
 @pytest.mark.parametrize("nodes,local", [(2, 2), (2, 4), (4, 2), (2, 8)])
 def test_hierarchical_matches_composed_sim(_env, nodes, local):
     """The full hierarchical flow (intra SRA -> leader cross reduction ->
     compressed intra broadcast) on hardware vs a composed CPU simulation.
     Covers the cross engine's independent reduction selection (default Ring
-    for >2 nodes) and the compressed broadcast — neither had ever executed
-    multi-rank on a GPU."""
+    for >2 nodes) and the compressed broadcast.  `loopback_hierarchical`
+    runs Reducer::allreduce, the call the backend makes per bucket."""
     from torch_cgx_amd import _C
     bits, bucket = 4, 512
     _cfg(_env, bits, bucket)
@@ -289,31 +309,56 @@ def test_hierarchical_matches_composed_sim(_env, nodes, local):
     torch.manual_seed(50 + ws)
     n = 20_000
     cpu = [torch.randn(n) for _ in range(ws)]
-
-    # composed expectation: per-node SRA, then cross reduction over the
-    # node results (SRA at 2 nodes — the engine's ring needs >2 — else
-    # Ring, the cross default), then the broadcast quantize round trip
-    node_res = []
-    for nd in range(nodes):
-        r = sra_sim.sra_allreduce(
-            [cpu[nd * local + k].clone() for k in range(local)],
-            [n], [(bits, bucket)])
-        node_res.append(r[0])
-    if nodes > 2:
-        cross = sra_sim.ring_allreduce([t.clone() for t in node_res],
-                                       [n], [(bits, bucket)])
-    else:
-        cross = sra_sim.sra_allreduce([t.clone() for t in node_res],
-                                      [n], [(bits, bucket)])
-    from torch_cgx_amd.ops import golden as g
-    leader = cross[0]
-    expected = g.dequantize(g.quantize(leader, bits, bucket, rand=0.5), n,
-                            torch.float32, bits, bucket)
+    expected = _composed_hier_sim(cpu, nodes, local, bits, bucket)
 
     buckets = [t.to(_dev()) for t in cpu]
     _C.loopback_hierarchical(buckets, local)
     for r in range(ws):
         assert torch.equal(buckets[r].cpu(), expected), (nodes, local, r)
+
+
+@pytest.fixture(scope="module")
+def intra_broadcast_case():
+    """nodes=2 x local=2, 4 bits, bucket 512, fp32, n=4099 (no multiple of
+    the bucket or of 4 ranks), deterministic rounding: the inputs and both
+    CPU expectations, flat (ws=4 SRA) and hierarchical (composed)."""
+    bits, bucket, n = 4, 512, 4099
+    torch.manual_seed(77)
+    cpu = [torch.randn(n) for _ in range(4)]
+    flat = sra_sim.sra_allreduce([t.clone() for t in cpu], [n],
+                                 [(bits, bucket)])
+    hier = _composed_hier_sim(cpu, 2, 2, bits, bucket)
+    # the two flows must be tell-apart-able on these inputs
+    assert not torch.equal(flat[0], hier)
+    return bits, bucket, cpu, flat, hier
+
+
+def test_intra_broadcast_off_takes_flat_path(_env, intra_broadcast_case):
+    """CGX_INTRA_BROADCAST=0 sends the multi-node reducer down the flat
+    path: bitwise the ws=4 SRA simulation, not the composed one."""
+    from torch_cgx_amd import _C
+    bits, bucket, cpu, flat, hier = intra_broadcast_case
+    _cfg(_env, bits, bucket)
+    _env["CGX_INTRA_BROADCAST"] = "0"
+    buckets = [t.to(_dev()) for t in cpu]
+    _C.loopback_hierarchical(buckets, 2)
+    for r in range(4):
+        got = buckets[r].cpu()
+        assert torch.equal(got, flat[r]), r
+        assert not torch.equal(got, hier), r
+
+
+def test_intra_broadcast_unset_takes_hierarchical_path(_env,
+                                                       intra_broadcast_case):
+    """Same call with the variable unset: the composed simulation."""
+    from torch_cgx_amd import _C
+    bits, bucket, cpu, _flat, hier = intra_broadcast_case
+    _cfg(_env, bits, bucket)
+    _env.pop("CGX_INTRA_BROADCAST", None)
+    buckets = [t.to(_dev()) for t in cpu]
+    _C.loopback_hierarchical(buckets, 2)
+    for r in range(4):
+        assert torch.equal(buckets[r].cpu(), hier), r
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])

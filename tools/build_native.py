@@ -23,12 +23,14 @@ SOURCES = [
     "csrc/phase_timer.cc",
     "csrc/engine.cc",
     "csrc/transport.cc",
+    "csrc/reducer.cc",
     "csrc/backend.cc",
     "csrc/bindings.cc",
 ]
 HEADERS = ["csrc/compress.h", "csrc/check.h", "csrc/config.h",
            "csrc/registry.h", "csrc/plan.h", "csrc/phase_timer.h",
-           "csrc/engine.h", "csrc/backend.h", "csrc/transport.h"]
+           "csrc/engine.h", "csrc/backend.h", "csrc/transport.h",
+           "csrc/reducer.h"]
 EXT_OUT = os.path.join(
     "torch_cgx_amd", "_C" + sysconfig.get_config_var("EXT_SUFFIX"))
 
