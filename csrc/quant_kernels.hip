@@ -1,33 +1,38 @@
 // CDNA4 (gfx950) max-min quantization kernels for the cgx backend.
 //
-// Design (MI355X-native, not a port):
-//  * wavefront = 64 lanes; one WAVE per quantization bucket — for buckets up
-//    to 2048 every lane's packs stay in registers between the meta and
-//    encode phases (single HBM read), the min/max reduction is a DPP row-op
-//    sequence; 16-bit dtypes reduce with packed v_pk_min/max; small
-//    power-of-two buckets (< 512) pack 64/(bucket/8) buckets per wave with
-//    segmented DPP reductions (QuantSub).
-//  * REGISTER-ISOLATED kernel family (the round-2 lesson, measured three
-//    times over): the register allocator sizes a kernel for its worst path,
-//    so the hot paths live in their own lean launches —
-//      k_quantize_fast  (53-89 VGPR; QuantRun, compile-time groups/lane)
-//      k_quantize_sub   (small buckets, multi-bucket-per-wave)
-//      k_quantize       (generic: error feedback, unaligned, partial-bucket
-//                        tails re-entering via kFlagTailOnly, bucket%8!=0
-//                        meta pass)
-//      k_dequant_fast   (56/33 VGPR; branch-free, incremental bucket index)
-//      k_dequant        (generic + ragged tails via kFlagTailOnly)
-//    The host router (compress.h route_quantize/route_dequantize) decides
-//    which kernel serves which slice; launch() at the end of this file
-//    dispatches a routed group.
+// The host router (compress.h route_quantize/route_dequantize) decides which
+// kernel serves which slice; launch() at the end of this file dispatches a
+// routed group.  The family is REGISTER-ISOLATED: the register allocator
+// sizes a kernel for its worst path, so each hot path is its own launch and
+// is kept at the allocation it was measured with (benchmarks/RESULTS.md).
+//
+//  pinned (hot) kernels
+//    k_quantize_fast  QuantRun: one wave per bucket, bucket % 8 == 0 and
+//                     <= 2048, so every lane's packs stay in registers
+//                     between the min/max reduction and the encode (single
+//                     HBM read); compile-time groups per lane; 16-bit
+//                     dtypes reduce with packed v_pk_min/max.
+//    k_quantize_sub   QuantSub: power-of-two buckets < 512 pack
+//                     64/(bucket/8) buckets per wave with segmented DPP
+//                     reductions.
+//    k_dequant_fast   bucket % 8 == 0, u32-indexable: one 16-byte store per
+//                     thread per iteration, incremental bucket index,
+//                     compile-time alignment/accumulate flags.
+//  generic (cold) kernels, one body each
+//    k_quantize       error feedback, unaligned input, bucket > 2048,
+//                     partial buckets (kFlagTailOnly) and, with
+//                     ENCODE=false, the meta pass of bucket % 8 != 0.
+//    k_pack_generic   the pack pass of bucket % 8 != 0.
+//    k_dequant        bucket % 8 != 0, slices of 2^31 or more elements and
+//                     ragged tails (kFlagTailOnly): decode_unit.
+//    k_residual_q/_d  raw skip_incomplete tails;  k_add  y += x.
+//
 //  * the numeric spec lives once: slice_geom (compress.h) for the wire
 //    layout, quant_level/encode_pack for encode, decode_raw/accum_raw for
 //    decode; every kernel inlines these.
-//  * memory-bound workload: 16-byte vectorized loads/stores wherever the
-//    slice base is 16B-aligned; decode uses 4 elems/thread for fp32 so every
-//    store is one coalesced float4; no integer division or per-access
-//    alignment branches in any hot loop (incremental bucket trackers,
-//    compile-time alignment/accumulate template flags).
+//  * memory-bound workload: 16-byte loads/stores wherever the base is
+//    16B-aligned, and no integer division in a hot loop.
+//  * min/max reductions are DPP row operations (seg_minmax), not shuffles.
 //  * stochastic rounding via a stateless splitmix64 hash per pack (no RNG
 //    state buffers, deterministic given the per-launch seed; the hash key is
 //    the GLOBAL pack index, so the kernel split is byte-transparent);
@@ -79,41 +84,50 @@ __device__ __forceinline__ float rand_lane(uint64_t pack_rand, int j) {
   return static_cast<float>((pack_rand >> (8 * j)) & 0xFF) * (1.0f / 256.0f);
 }
 
-// Full-wave min/max reduction via DPP row operations (register path, ~2
-// cycles/step) instead of __shfl_xor, which hipcc lowers to six dependent
-// ds_bpermute_b32 (LDS latency) per value -- the dominant cost of the
-// original wave-per-bucket kernel.
-// Sequence: row_shr 1/2/4/8 then row_bcast15/31; lane 63 holds the result.
-#define CGX_DPP_STEP(CTRL, OP)                                                t = __builtin_amdgcn_update_dpp(iid, __builtin_bit_cast(int, v), (CTRL),                                    0xf, 0xf, false);                           v = OP(v, __builtin_bit_cast(float, t));
+// Min/max reduction over aligned segments of L lanes (a power of two; L = 64
+// is the whole wave) via DPP row operations (register path, ~2 cycles/step)
+// instead of __shfl_xor, which hipcc lowers to six dependent ds_bpermute_b32
+// (LDS latency) per value.  Ladder: row_shr 1/2/4/8, row_bcast 15/31,
+// truncated at L; the segment's last lane then holds its result, which is
+// handed to every lane by readlane 63 (L = 64) or one ds_bpermute.
+template <int CTRL, bool MAX>
+__device__ __forceinline__ float dpp_step(float v) {
+  const int ident = __builtin_bit_cast(int, MAX ? -INFINITY : INFINITY);
+  const float t = __builtin_bit_cast(
+      float, __builtin_amdgcn_update_dpp(ident, __builtin_bit_cast(int, v),
+                                         CTRL, 0xf, 0xf, false));
+  return MAX ? fmaxf(v, t) : fminf(v, t);
+}
 
-__device__ __forceinline__ void wave_minmax(float& vmin, float& vmax) {
-  int t;
-  {
-    const int iid = __builtin_bit_cast(int, INFINITY);
-    float v = vmin;
-    CGX_DPP_STEP(0x111, fminf)  // row_shr:1
-    CGX_DPP_STEP(0x112, fminf)  // row_shr:2
-    CGX_DPP_STEP(0x114, fminf)  // row_shr:4
-    CGX_DPP_STEP(0x118, fminf)  // row_shr:8
-    CGX_DPP_STEP(0x142, fminf)  // row_bcast:15
-    CGX_DPP_STEP(0x143, fminf)  // row_bcast:31
-    vmin = __builtin_bit_cast(
-        float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-  }
-  {
-    const int iid = __builtin_bit_cast(int, -INFINITY);
-    float v = vmax;
-    CGX_DPP_STEP(0x111, fmaxf)
-    CGX_DPP_STEP(0x112, fmaxf)
-    CGX_DPP_STEP(0x114, fmaxf)
-    CGX_DPP_STEP(0x118, fmaxf)
-    CGX_DPP_STEP(0x142, fmaxf)
-    CGX_DPP_STEP(0x143, fmaxf)
-    vmax = __builtin_bit_cast(
-        float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+template <int L, bool MAX>
+__device__ __forceinline__ float dpp_ladder(float v) {
+  if constexpr (L >= 2) v = dpp_step<0x111, MAX>(v);   // row_shr:1
+  if constexpr (L >= 4) v = dpp_step<0x112, MAX>(v);   // row_shr:2
+  if constexpr (L >= 8) v = dpp_step<0x114, MAX>(v);   // row_shr:4
+  if constexpr (L >= 16) v = dpp_step<0x118, MAX>(v);  // row_shr:8
+  if constexpr (L >= 32) v = dpp_step<0x142, MAX>(v);  // row_bcast:15
+  if constexpr (L >= 64) v = dpp_step<0x143, MAX>(v);  // row_bcast:31
+  return v;
+}
+
+// The statement order below (for the whole wave: min ladder, readlane, max
+// ladder, readlane) is the one the pinned kernels were measured with.
+template <int L>
+__device__ __forceinline__ void seg_minmax(float& vmin, float& vmax,
+                                           int lane) {
+  if constexpr (L == kWave) {
+    const int imin = __builtin_bit_cast(int, dpp_ladder<L, false>(vmin));
+    vmin = __builtin_bit_cast(float, __builtin_amdgcn_readlane(imin, 63));
+    const int imax = __builtin_bit_cast(int, dpp_ladder<L, true>(vmax));
+    vmax = __builtin_bit_cast(float, __builtin_amdgcn_readlane(imax, 63));
+  } else if constexpr (L > 1) {
+    const int imin = __builtin_bit_cast(int, dpp_ladder<L, false>(vmin));
+    const int imax = __builtin_bit_cast(int, dpp_ladder<L, true>(vmax));
+    const int src = ((lane / L) * L + (L - 1)) * 4;
+    vmin = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src, imin));
+    vmax = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src, imax));
   }
 }
-#undef CGX_DPP_STEP
 
 template <typename To, typename From>
 __device__ __forceinline__ To bitcast(From f) {
@@ -278,30 +292,22 @@ __device__ __forceinline__ SliceGeom geom_of(int64_t n, int32_t bucket,
 // the fp16/bf16 quantize was 87% VALU-busy with per-element convert+min+max;
 // packed ops process 2 elements per instruction without unpacking.
 template <typename T>
-struct Pk2;
+struct Pk2Elem;
 template <>
-struct Pk2<__half> {
-  using P = _Float16 __attribute__((ext_vector_type(2)));
-  static constexpr uint32_t kInf = 0x7C007C00u;   // +inf, +inf
-  static constexpr uint32_t kNInf = 0xFC00FC00u;  // -inf, -inf
-  static __device__ __forceinline__ P min(P a, P b) {
-    return __builtin_elementwise_min(a, b);
-  }
-  static __device__ __forceinline__ P max(P a, P b) {
-    return __builtin_elementwise_max(a, b);
-  }
-  static __device__ __forceinline__ float lo(P v) {
-    return static_cast<float>(v[0]);
-  }
-  static __device__ __forceinline__ float hi(P v) {
-    return static_cast<float>(v[1]);
-  }
+struct Pk2Elem<__half> {
+  using type = _Float16;
+  static constexpr uint32_t kInf = 0x7C00u;
 };
 template <>
-struct Pk2<__hip_bfloat16> {
-  using P = __bf16 __attribute__((ext_vector_type(2)));
-  static constexpr uint32_t kInf = 0x7F807F80u;
-  static constexpr uint32_t kNInf = 0xFF80FF80u;
+struct Pk2Elem<__hip_bfloat16> {
+  using type = __bf16;
+  static constexpr uint32_t kInf = 0x7F80u;
+};
+template <typename T>
+struct Pk2 {
+  using P = typename Pk2Elem<T>::type __attribute__((ext_vector_type(2)));
+  static constexpr uint32_t kInf = Pk2Elem<T>::kInf * 0x10001u;  // +inf, +inf
+  static constexpr uint32_t kNInf = kInf | 0x80008000u;          // -inf, -inf
   static __device__ __forceinline__ P min(P a, P b) {
     return __builtin_elementwise_min(a, b);
   }
@@ -316,65 +322,96 @@ struct Pk2<__hip_bfloat16> {
   }
 };
 
-// 8-element vector load/store (one pack).  aligned16 is wave-uniform for the
-// quantize kernel (slice bases are pack-aligned) and per-thread for dequant.
-template <typename T>
-__device__ __forceinline__ void load8(const T* p, bool aligned16,
-                                      uint32_t (&r)[8]) {
-  if constexpr (sizeof(T) == 4) {
-    if (aligned16) {
-      int4 a = *reinterpret_cast<const int4*>(p);
-      int4 b = *reinterpret_cast<const int4*>(p + 4);
-      r[0] = a.x; r[1] = a.y; r[2] = a.z; r[3] = a.w;
-      r[4] = b.x; r[5] = b.y; r[6] = b.z; r[7] = b.w;
-      return;
-    }
+using v4u = uint32_t __attribute__((ext_vector_type(4)));
+
+// Compile-time-aligned 16-byte load/store (a runtime alignment flag compiles
+// into per-dword flat accesses inside a hot loop).
+template <bool AL16>
+__device__ __forceinline__ void load16B(const void* p, uint32_t (&r)[4]) {
+  if constexpr (AL16) {
+    const v4u a = *reinterpret_cast<const v4u*>(
+        __builtin_assume_aligned(p, 16));
+    r[0] = a.x; r[1] = a.y; r[2] = a.z; r[3] = a.w;
   } else {
-    if (aligned16) {
-      int4 a = *reinterpret_cast<const int4*>(p);
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+#pragma unroll
+    for (int j = 0; j < 4; j++) r[j] = q[j];
+  }
+}
+
+template <bool AL16>
+__device__ __forceinline__ void store16B(void* p, const uint32_t (&r)[4]) {
+  if constexpr (AL16) {
+    v4u a;
+    a.x = r[0]; a.y = r[1]; a.z = r[2]; a.w = r[3];
+    *reinterpret_cast<v4u*>(__builtin_assume_aligned(p, 16)) = a;
+  } else {
+    uint32_t* q = reinterpret_cast<uint32_t*>(p);
+#pragma unroll
+    for (int j = 0; j < 4; j++) q[j] = r[j];
+  }
+}
+
+// First m >= 1 of N raw values at p (the rest repeat the first, so a min/max
+// over all N needs no mask), for the generic kernels
+// and QuantSub: 16-byte accesses when all N are there and p is 16B-aligned,
+// element accesses otherwise -- a 16-bit base that is only 2-byte aligned
+// must not be touched with 32-bit accesses.  N * sizeof(T) is 16 or 32.
+// (Plain int4 accesses: through load16B<true> every k_quantize_sub
+// instantiation compiles to other code than it was measured with.)
+template <typename T, int N>
+__device__ __forceinline__ void load_vec(const T* p, bool aligned16, int m,
+                                         uint32_t (&r)[N]) {
+  constexpr int E = 16 / sizeof(T);
+  if (m == N && aligned16) {
+#pragma unroll
+    for (int c = 0; c < N; c += E) {
+      const int4 a = *reinterpret_cast<const int4*>(p + c);
       const uint32_t w[4] = {static_cast<uint32_t>(a.x),
                              static_cast<uint32_t>(a.y),
                              static_cast<uint32_t>(a.z),
                              static_cast<uint32_t>(a.w)};
 #pragma unroll
-      for (int j = 0; j < 8; j++) r[j] = (w[j >> 1] >> ((j & 1) * 16)) & 0xFFFF;
-      return;
+      for (int j = 0; j < E; j++) {
+        if constexpr (sizeof(T) == 4) r[c + j] = w[j];
+        else r[c + j] = (w[j >> 1] >> ((j & 1) * 16)) & 0xFFFF;
+      }
     }
+    return;
   }
-  using R = typename RawOf<T>::type;
-  const R* q = reinterpret_cast<const R*>(p);
+  const auto* q = reinterpret_cast<const typename RawOf<T>::type*>(p);
+  if (m == N) {
 #pragma unroll
-  for (int j = 0; j < 8; j++) r[j] = q[j];
+    for (int j = 0; j < N; j++) r[j] = q[j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < N; j++) r[j] = q[j < m ? j : 0];
+  }
 }
 
-template <typename T>
-__device__ __forceinline__ void store8(T* p, bool aligned16,
-                                       const uint32_t (&r)[8]) {
-  if constexpr (sizeof(T) == 4) {
-    if (aligned16) {
-      int4 a = {static_cast<int>(r[0]), static_cast<int>(r[1]),
-                static_cast<int>(r[2]), static_cast<int>(r[3])};
-      int4 b = {static_cast<int>(r[4]), static_cast<int>(r[5]),
-                static_cast<int>(r[6]), static_cast<int>(r[7])};
-      *reinterpret_cast<int4*>(p) = a;
-      *reinterpret_cast<int4*>(p + 4) = b;
-      return;
+template <typename T, int N>
+__device__ __forceinline__ void store_vec(T* p, bool aligned16, int m,
+                                          const uint32_t (&r)[N]) {
+  constexpr int E = 16 / sizeof(T);
+  if (m == N && aligned16) {
+#pragma unroll
+    for (int c = 0; c < N; c += E) {
+      int w[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        if constexpr (sizeof(T) == 4) w[j] = r[c + j];
+        else w[j] = r[c + 2 * j] | (r[c + 2 * j + 1] << 16);
+      }
+      *reinterpret_cast<int4*>(p + c) = int4{w[0], w[1], w[2], w[3]};
     }
-  } else {
-    if (aligned16) {
-      int4 a;
-      a.x = static_cast<int>(r[0] | (r[1] << 16));
-      a.y = static_cast<int>(r[2] | (r[3] << 16));
-      a.z = static_cast<int>(r[4] | (r[5] << 16));
-      a.w = static_cast<int>(r[6] | (r[7] << 16));
-      *reinterpret_cast<int4*>(p) = a;
-      return;
-    }
+    return;
   }
   using R = typename RawOf<T>::type;
   R* q = reinterpret_cast<R*>(p);
 #pragma unroll
-  for (int j = 0; j < 8; j++) q[j] = static_cast<R>(r[j]);
+  for (int j = 0; j < N; j++) {
+    if (j < m) q[j] = static_cast<R>(r[j]);
+  }
 }
 
 // Write the low `nb` bytes of v to p (little-endian), widest aligned stores.
@@ -449,11 +486,7 @@ struct QuantRun {
   int slice_idx;
 
   __device__ __forceinline__ void load(Stash& s, int64_t lb) const {
-    load_from(s, base + lb * (int64_t)(ngroups * 8));
-  }
-
-  // arbitrary 16B-aligned source (global or LDS via generic pointer)
-  __device__ __forceinline__ void load_from(Stash& s, const T* in) const {
+    const T* in = base + lb * (int64_t)(ngroups * 8);
 #pragma unroll
     for (int k = 0; k < G; k++) {
       const int g = lane + k * kWave;
@@ -512,7 +545,7 @@ struct QuantRun {
         }
       }
     }
-    wave_minmax(lmin, lmax);
+    seg_minmax<kWave>(lmin, lmax, lane);
     const uint32_t unit_raw = f2raw<T>((lmax - lmin) / divisor);
     const float unitf = raw2f<T>(unit_raw);
     const float minf = lmin;
@@ -559,50 +592,8 @@ struct QuantRun {
 // power of two < 64): the wave-per-bucket layout leaves (64-L) lanes idle
 // and serializes 64/L x more buckets per wave; here the wave processes
 // W = 64/L buckets at once, reducing each L-lane segment with the DPP
-// ladder truncated at L and broadcasting the segment result back with one
-// ds_bpermute per value.  Bucket 256 measured 1.3-2.4 TB/s on the
-// wave-per-bucket path; this recovers most of the bucket-1024 rate.
-template <int L>
-__device__ __forceinline__ void seg_minmax(float& vmin, float& vmax,
-                                           int lane) {
-  if constexpr (L > 1) {
-    int t;
-#define CGX_DPP_SEG(CTRL, OP, IDENT)                                       \
-  t = __builtin_amdgcn_update_dpp(IDENT, __builtin_bit_cast(int, v),       \
-                                  (CTRL), 0xf, 0xf, false);                \
-  v = OP(v, __builtin_bit_cast(float, t));
-    {
-      const int iid = __builtin_bit_cast(int, INFINITY);
-      float v = vmin;
-      CGX_DPP_SEG(0x111, fminf, iid)
-      if constexpr (L >= 4) CGX_DPP_SEG(0x112, fminf, iid)
-      if constexpr (L >= 8) CGX_DPP_SEG(0x114, fminf, iid)
-      if constexpr (L >= 16) CGX_DPP_SEG(0x118, fminf, iid)
-      if constexpr (L >= 32) CGX_DPP_SEG(0x142, fminf, iid)
-      vmin = v;
-    }
-    {
-      const int iid = __builtin_bit_cast(int, -INFINITY);
-      float v = vmax;
-      CGX_DPP_SEG(0x111, fmaxf, iid)
-      if constexpr (L >= 4) CGX_DPP_SEG(0x112, fmaxf, iid)
-      if constexpr (L >= 8) CGX_DPP_SEG(0x114, fmaxf, iid)
-      if constexpr (L >= 16) CGX_DPP_SEG(0x118, fmaxf, iid)
-      if constexpr (L >= 32) CGX_DPP_SEG(0x142, fmaxf, iid)
-      vmax = v;
-    }
-#undef CGX_DPP_SEG
-    // segment result sits at lane (s+1)*L-1; broadcast it to the segment
-    const int src = ((lane / L) * L + (L - 1)) * 4;
-    vmin = __builtin_bit_cast(
-        float, __builtin_amdgcn_ds_bpermute(src,
-                                            __builtin_bit_cast(int, vmin)));
-    vmax = __builtin_bit_cast(
-        float, __builtin_amdgcn_ds_bpermute(src,
-                                            __builtin_bit_cast(int, vmax)));
-  }
-}
-
+// ladder truncated at L (seg_minmax<L>).  Bucket 256 measured 1.3-2.4 TB/s
+// on the wave-per-bucket path; this recovers most of the bucket-1024 rate.
 template <typename T, int BITS, int L>
 struct QuantSub {
   using R = typename RawOf<T>::type;
@@ -627,7 +618,7 @@ struct QuantSub {
       float lmin = INFINITY, lmax = -INFINITY;
       if (active) {
         const T* in = base + lb * (int64_t)(L * 8) + li * 8;
-        load8<T>(in, true, r);
+        load_vec<T, 8>(in, true, 8, r);
 #pragma unroll
         for (int j = 0; j < 8; j++) {
           const float f = raw2f<T>(r[j]);
@@ -667,8 +658,8 @@ struct QuantSub {
 
 // Lean fast-path kernel (see compress.h LaunchKind kFast): only the
 // QuantRun register path is instantiated, so the register allocator is not
-// forced to the generic/EF paths' footprint (k_quantize<float,4,true>
-// allocates 139 VGPRs = 3 waves/SIMD; this kernel ~half that).
+// forced to the generic/EF paths' footprint (k_quantize<T,BITS,true> runs
+// at 4 waves/SIMD; this kernel at 5-8).
 template <typename T, int BITS, int MAXGT>
 __global__ __launch_bounds__(kThreads) void k_quantize_fast(
     const QuantDesc* __restrict__ descs, const int64_t* __restrict__ cum,
@@ -762,6 +753,23 @@ __global__ __launch_bounds__(kThreads) void k_quantize_sub(
   }
 }
 
+// First m values of pack g of a bucket as the quantizer sees them: x, plus
+// the error-feedback residual when there is one, rounded to T (the rest
+// repeat the first).
+template <typename T>
+__device__ __forceinline__ void load_pack(const T* in, const T* fbp,
+                                          bool al16, bool al16_fb, int g,
+                                          int m, uint32_t (&r)[8]) {
+  load_vec<T, 8>(in + g * 8, al16, m, r);
+  if (fbp) {
+    uint32_t f[8];
+    load_vec<T, 8>(fbp + g * 8, al16_fb, m, f);
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+      r[j] = f2raw<T>(raw2f<T>(r[j]) + raw2f<T>(f[j]));
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Quantize: one wave per bucket.  ENCODE=true requires bucket % 8 == 0 for
 // every slice (host guarantees); ENCODE=false computes meta only (the
@@ -794,56 +802,28 @@ __global__ __launch_bounds__(kThreads) void k_quantize(
     const bool al16 = (reinterpret_cast<uintptr_t>(in) & 15) == 0;
     const int ngroups = (cur + 7) >> 3;
 
+    // fb alignment is independent of the input's (the engine rebases the
+    // phase-2 feedback base by a partition offset), so probe it separately
+    T* const fbp = d.fb ? reinterpret_cast<T*>(d.fb) + bstart : nullptr;
+    const bool al16_fb = (reinterpret_cast<uintptr_t>(fbp) & 15) == 0;
     uint32_t stash[MAXG][8];
     float lmin = INFINITY, lmax = -INFINITY;
-    const bool full = cur == d.bucket && (cur & 7) == 0 && al16;
-    T* const fbp = d.fb ? reinterpret_cast<T*>(d.fb) + bstart : nullptr;
-    if (full && ngroups <= MAXG * kWave && fbp) {
-      // error-feedback: stash the T-rounded x+fb and reduce over it.
-      // fb alignment is independent of the input's (the engine rebases the
-      // phase-2 feedback base by a partition offset), so probe it separately.
-      const bool al16_fb = (reinterpret_cast<uintptr_t>(fbp) & 15) == 0;
-      for (int g = lane, gi = 0; g < ngroups; g += kWave, gi++) {
-        uint32_t xr[8], fr[8];
-        load8<T>(in + g * 8, true, xr);
-        load8<T>(fbp + g * 8, al16_fb, fr);
+    for (int g = lane, gi = 0; g < ngroups; g += kWave, gi++) {
+      uint32_t r[8];
+      const int m = min(8, cur - g * 8);
+      load_pack<T>(in, fbp, al16, al16_fb, g, m, r);
+      if (gi < MAXG) {
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-          const uint32_t xe = f2raw<T>(raw2f<T>(xr[j]) + raw2f<T>(fr[j]));
-          stash[gi][j] = xe;
-          const float f = raw2f<T>(xe);
-          lmin = fminf(lmin, f);
-          lmax = fmaxf(lmax, f);
-        }
+        for (int j = 0; j < 8; j++) stash[gi][j] = r[j];
       }
-    } else {
-      for (int g = lane, gi = 0; g < ngroups; g += kWave, gi++) {
-        uint32_t r[8];
-        const int m = min(8, cur - g * 8);
-        if (m == 8) {
-          load8<T>(in + g * 8, al16, r);
-        } else {
-          const R* q = reinterpret_cast<const R*>(in) + g * 8;
-          for (int j = 0; j < m; j++) r[j] = q[j];
-          for (int j = m; j < 8; j++) r[j] = 0;
-        }
-        if (fbp) {
-          const R* q = reinterpret_cast<const R*>(fbp) + g * 8;
-          for (int j = 0; j < m; j++)
-            r[j] = f2raw<T>(raw2f<T>(r[j]) + raw2f<T>(q[j]));
-        }
-        if (gi < MAXG) {
 #pragma unroll
-          for (int j = 0; j < 8; j++) stash[gi][j] = r[j];
-        }
-        for (int j = 0; j < m; j++) {
-          const float f = raw2f<T>(r[j]);
-          lmin = fminf(lmin, f);
-          lmax = fmaxf(lmax, f);
-        }
+      for (int j = 0; j < 8; j++) {  // r[j >= m] repeats r[0]
+        const float f = raw2f<T>(r[j]);
+        lmin = fminf(lmin, f);
+        lmax = fmaxf(lmax, f);
       }
     }
-    wave_minmax(lmin, lmax);
+    seg_minmax<kWave>(lmin, lmax, lane);
     const uint32_t unit_raw = f2raw<T>((lmax - lmin) / divisor);
     const float unitf = raw2f<T>(unit_raw);
     const float minf = lmin;
@@ -864,16 +844,8 @@ __global__ __launch_bounds__(kThreads) void k_quantize(
         if (gi < MAXG) {
 #pragma unroll
           for (int j = 0; j < 8; j++) r[j] = stash[gi][j];
-        } else if (m == 8 && !fbp) {
-          load8<T>(in + g * 8, al16, r);
         } else {
-          const R* q = reinterpret_cast<const R*>(in) + g * 8;
-          for (int j = 0; j < m; j++) r[j] = q[j];
-          if (fbp) {
-            const R* f = reinterpret_cast<const R*>(fbp) + g * 8;
-            for (int j = 0; j < m; j++)
-              r[j] = f2raw<T>(raw2f<T>(r[j]) + raw2f<T>(f[j]));
-          }
+          load_pack<T>(in, fbp, al16, al16_fb, g, m, r);
         }
         uint64_t value = 0;
         uint32_t lv[8] = {};
@@ -1000,47 +972,6 @@ __device__ __forceinline__ uint64_t load_pack_full(
   } else {
     return load_bytes(src + g * BITS, BITS);
   }
-}
-
-using v4u = uint32_t __attribute__((ext_vector_type(4)));
-
-// Compile-time-aligned 16-byte load/store (the runtime-bool forms compile
-// into per-dword flat accesses inside the hot loop).
-template <bool AL16>
-__device__ __forceinline__ void load16B(const void* p, uint32_t (&r)[4]) {
-  if constexpr (AL16) {
-    const v4u a = *reinterpret_cast<const v4u*>(
-        __builtin_assume_aligned(p, 16));
-    r[0] = a.x; r[1] = a.y; r[2] = a.z; r[3] = a.w;
-  } else {
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-#pragma unroll
-    for (int j = 0; j < 4; j++) r[j] = q[j];
-  }
-}
-
-template <bool AL16>
-__device__ __forceinline__ void store16B(void* p, const uint32_t (&r)[4]) {
-  if constexpr (AL16) {
-    v4u a;
-    a.x = r[0]; a.y = r[1]; a.z = r[2]; a.w = r[3];
-    *reinterpret_cast<v4u*>(__builtin_assume_aligned(p, 16)) = a;
-  } else {
-    uint32_t* q = reinterpret_cast<uint32_t*>(p);
-#pragma unroll
-    for (int j = 0; j < 4; j++) q[j] = r[j];
-  }
-}
-
-// Runtime-alignment forms, for the generic kernel only.
-__device__ __forceinline__ void load16B(const void* p, bool al16,
-                                        uint32_t (&r)[4]) {
-  if (al16) load16B<true>(p, r); else load16B<false>(p, r);
-}
-
-__device__ __forceinline__ void store16B(void* p, bool al16,
-                                         const uint32_t (&r)[4]) {
-  if (al16) store16B<true>(p, r); else store16B<false>(p, r);
 }
 
 // Incremental bucket-index tracker: replaces the per-iteration integer
@@ -1199,9 +1130,9 @@ __device__ void deq_16_fast(const DequantDesc& d,
 }
 
 // Lean dequantize kernel: only the branch-free fast paths (bucket%8==0,
-// u32-indexable slices) are instantiated — the fused k_dequant allocates
-// 102 VGPRs (fp32) because the register allocator must also cover the
-// generic/tail paths; ragged tails re-enter k_dequant with kFlagTailOnly.
+// u32-indexable slices) are instantiated, so the register allocator does
+// not have to cover the generic/tail paths; ragged tails re-enter k_dequant
+// with kFlagTailOnly.
 template <typename T, int BITS>
 __global__ __launch_bounds__(kThreads) void k_dequant_fast(
     const DequantDesc* __restrict__ descs, int nslices) {
@@ -1264,214 +1195,74 @@ __global__ __launch_bounds__(kThreads) void k_dequant_fast(
   }
 }
 
-// ---------------------------------------------------------------------------
-// Dequantize(+multi-source accumulate): grid-stride threads over packs.
-// Sums d.nsrc compressed streams in T precision in stream order (matching the
-// CPU simulation's per-source sequential accumulate), optionally on top of
-// the existing output values (d.add).
-// ---------------------------------------------------------------------------
+// Decode the first m elements (all E for a full unit) of unit w of a slice:
+// E = 16 / sizeof(T) elements, so a full unit is one 16-byte store and lies
+// inside one pack.  The d.nsrc streams are summed in T precision in stream
+// order (matching the CPU simulation's per-source sequential accumulate), on
+// top of the existing output when d.add.  Any bucket size: the bucket index
+// is divided out once per unit and stepped per element.
+template <typename T, int BITS>
+__device__ __forceinline__ void decode_unit(const DequantDesc& d,
+                                            const SliceGeom& sg, bool al16,
+                                            int64_t w, int m) {
+  using R = typename RawOf<T>::type;
+  constexpr int E = 16 / sizeof(T);
+  const int64_t e0 = w * E;
+  const int64_t gb = (e0 >> 3) * BITS;  // byte offset of the unit's pack
+  const int shift = static_cast<int>(e0 & 7) * BITS;
+  const int nbytes = static_cast<int>(
+      min(static_cast<int64_t>(BITS), sg.packed_bytes - gb));
+  const int64_t bk0 = e0 / d.bucket;
+  const int rem0 = static_cast<int>(e0 - bk0 * d.bucket);
+  const bool have = d.add != 0;
+  T* outp = reinterpret_cast<T*>(d.out) + e0;
+  uint32_t v[E];
+  if (have) load_vec<T, E>(outp, al16, m, v);
+  for (int sidx = 0; sidx < d.nsrc; sidx++) {
+    const R* meta = reinterpret_cast<const R*>(d.in + sidx * d.src_stride);
+    const uint64_t value =
+        load_bytes(d.in + sidx * d.src_stride + sg.meta_bytes + gb, nbytes) >>
+        shift;
+    int64_t bk = bk0;
+    int rem = rem0;
+    uint32_t ur, mr;
+    load_meta_pair<R>(meta, bk, ur, mr);
+#pragma unroll
+    for (int j = 0; j < E; j++) {
+      if (j >= m) break;
+      if (j > 0 && ++rem == d.bucket) {  // crossed into the next bucket
+        rem = 0;
+        load_meta_pair<R>(meta, ++bk, ur, mr);
+      }
+      accum_raw<T>(v[j], !have && sidx == 0,
+                   decode_raw<T>(ur, mr, pack_level<BITS>(value, j)));
+    }
+  }
+  store_vec<T, E>(outp, al16, m, v);
+}
+
+// Generic dequantize (+ multi-source accumulate): grid-stride threads over
+// full units, then thread 0 decodes the ragged remainder.  kFlagTailOnly:
+// k_dequant_fast already decoded the full units.
 template <typename T, int BITS>
 __global__ __launch_bounds__(kThreads) void k_dequant(
     const DequantDesc* __restrict__ descs, int nslices) {
-  // Outer loop over slices with every per-slice quantity hoisted; the inner
-  // grid-stride loop over FULL groups is branch-free (no tail/alignment
-  // checks, no exec-mask divergence) -- the original per-group binary-search
-  // form spent >80% of its instructions on repeated int64 address math.
-  using R = typename RawOf<T>::type;
+  constexpr int E = 16 / sizeof(T);
   const int64_t t0 =
       static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   for (int si = 0; si < nslices; si++) {
     const DequantDesc d = descs[si];
     const SliceGeom sg = geom_of<T>(d.n, d.bucket, d.flags, BITS);
-    const int64_t nq = sg.nq;
-    const int64_t meta_bytes = sg.meta_bytes;
-    const int64_t full_groups = nq >> 3;
-    const bool oneb = (d.bucket & 7) == 0;
-    const uint32_t B8 = oneb ? static_cast<uint32_t>(d.bucket >> 3) : 1u;
     const bool al16 = (reinterpret_cast<uintptr_t>(d.out) & 15) == 0;
-    const bool small = nq < (int64_t(1) << 31);
-    T* const out_base = reinterpret_cast<T*>(d.out);
-    const uint8_t* const in0 = d.in + meta_bytes;  // packed base, source 0
-
-    if constexpr (sizeof(T) == 4) {
-      // fp32: 4 elements per thread -- ONE coalesced float4 per lane
-      // (8-wide fp32 needs two 16B stores at 32B lane stride, which measured
-      // 3x slower per element than the fp16 path's single int4)
-      const int64_t full_subs = nq >> 2;
-      const uint32_t B4 = oneb ? static_cast<uint32_t>(d.bucket >> 2) : 1u;
-      // kFlagTailOnly: k_dequant_fast already decoded the full 4-elem subs
-      if (d.flags & kFlagTailOnly) goto f32_tail;
-      {
-      // two grid-stride iterations in flight (U=4 measured 0.170 ms vs
-      // 0.142 at U=2 for 64M/4-bit: the extra registers cost more occupancy
-      // than the added chains buy in latency hiding)
-      constexpr int U = 2;
-      int64_t w = t0;
-      for (; w + (U - 1) * stride < full_subs; w += U * stride) {
-        int64_t ws2[U];
-        uint32_t v[U][4];
-        const bool have = d.add != 0;
-        float* outp[U];
-        uint32_t bk0[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-          ws2[u] = w + u * stride;
-          outp[u] = reinterpret_cast<float*>(d.out) + ws2[u] * 4;
-          if (have) load16B(outp[u], al16, v[u]);
-          bk0[u] = oneb
-                       ? (small ? static_cast<uint32_t>(ws2[u]) / B4
-                                : static_cast<uint32_t>(
-                                      ws2[u] / static_cast<int64_t>(B4)))
-                       : 0;
-        }
-        for (int sidx = 0; sidx < d.nsrc; sidx++) {
-          const uint8_t* src = in0 + sidx * d.src_stride;
-          const R* meta = reinterpret_cast<const R*>(src - meta_bytes);
-          uint64_t value[U];
-#pragma unroll
-          for (int u = 0; u < U; u++) {
-            const int64_t g = ws2[u] >> 1;
-            const int h = static_cast<int>(ws2[u] & 1);
-            // half-pack loads for even BITS (a full-pack load + register
-            // shift, which reads each pack twice, measured 0.156 ms vs
-            // 0.142 for 64M/4-bit: the doubled L1 traffic costs more than
-            // the narrower load saves)
-            if constexpr ((BITS & 1) == 0) {
-              value[u] = load_bytes(src + g * BITS + h * (BITS / 2), BITS / 2);
-            } else {
-              value[u] = load_bytes(src + g * BITS, BITS) >> (h * 4 * BITS);
-            }
-          }
-#pragma unroll
-          for (int u = 0; u < U; u++) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-              const int64_t bk = oneb ? bk0[u] : (ws2[u] * 4 + j) / d.bucket;
-              accum_raw<T>(v[u][j], !have && sidx == 0,
-                           decode_raw<T>(meta[2 * bk], meta[2 * bk + 1],
-                                         pack_level<BITS>(value[u], j)));
-            }
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) store16B(outp[u], al16, v[u]);
-      }
-      for (; w < full_subs; w += stride) {
-        const int64_t g = w >> 1;
-        const int h = static_cast<int>(w & 1);
-        uint32_t v[4];
-        bool have = d.add != 0;
-        float* outp = reinterpret_cast<float*>(d.out) + w * 4;
-        if (have) load16B(outp, al16, v);
-        const uint32_t bk0 =
-            oneb ? (small ? static_cast<uint32_t>(w) / B4
-                          : static_cast<uint32_t>(
-                                w / static_cast<int64_t>(B4)))
-                 : 0;
-        for (int sidx = 0; sidx < d.nsrc; sidx++) {
-          const uint8_t* src = in0 + sidx * d.src_stride;
-          const R* meta = reinterpret_cast<const R*>(src - meta_bytes);
-          uint64_t value;
-          if constexpr ((BITS & 1) == 0) {
-            value = load_bytes(src + g * BITS + h * (BITS / 2), BITS / 2);
-          } else {
-            value = load_bytes(src + g * BITS, BITS) >> (h * 4 * BITS);
-          }
-          uint32_t u0 = 0, m0 = 0;
-          if (oneb) load_meta_pair<R>(meta, bk0, u0, m0);
-#pragma unroll
-          for (int j = 0; j < 4; j++) {
-            uint32_t ur = u0, mr = m0;
-            if (!oneb) {
-              const int64_t bk = (w * 4 + j) / d.bucket;
-              load_meta_pair<R>(meta, bk, ur, mr);
-            }
-            accum_raw<T>(v[j], !have && sidx == 0,
-                         decode_raw<T>(ur, mr, pack_level<BITS>(value, j)));
-          }
-        }
-        store16B(outp, al16, v);
-      }
-      }  // generic fp32 path
-    f32_tail:
-      // scalar tail: elements [full_subs*4, nq)
-      if ((nq & 3) && t0 == 0) {
-        R* outr = reinterpret_cast<R*>(d.out);
-        for (int64_t eidx = full_subs * 4; eidx < nq; eidx++) {
-          const int64_t g = eidx >> 3;
-          const int j = static_cast<int>(eidx & 7);
-          const int nbytes = static_cast<int>(
-              min(static_cast<int64_t>(BITS), sg.packed_bytes - g * BITS));
-          const int64_t bk = eidx / d.bucket;
-          uint32_t v = d.add ? outr[eidx] : 0;
-          for (int sidx = 0; sidx < d.nsrc; sidx++) {
-            const uint8_t* src = in0 + sidx * d.src_stride;
-            const R* meta = reinterpret_cast<const R*>(src - meta_bytes);
-            const uint64_t value = load_bytes(src + g * BITS, nbytes);
-            accum_raw<T>(v, sidx == 0 && !d.add,
-                         decode_raw<T>(meta[2 * bk], meta[2 * bk + 1],
-                                       pack_level<BITS>(value, j)));
-          }
-          outr[eidx] = static_cast<R>(v);
-        }
-      }
-      continue;  // next slice (16-bit loop below is for 2-byte dtypes)
+    const int64_t full_units = sg.nq / E;
+    if (!(d.flags & kFlagTailOnly)) {
+      for (int64_t w = t0; w < full_units; w += stride)
+        decode_unit<T, BITS>(d, sg, al16, w, E);
     }
-    // kFlagTailOnly: k_dequant_fast already decoded the full 8-elem groups
-    if (d.flags & kFlagTailOnly) goto tail16;
-    for (int64_t g = t0; g < full_groups; g += stride) {
-      uint32_t v[8];
-      bool have = d.add != 0;
-      T* outp = out_base + g * 8;
-      if (have) load8<T>(outp, al16, v);
-      const uint32_t bk0 =
-          oneb ? (small ? static_cast<uint32_t>(g) / B8
-                        : static_cast<uint32_t>(g / static_cast<int64_t>(B8)))
-               : 0;
-      for (int sidx = 0; sidx < d.nsrc; sidx++) {
-        const uint8_t* src = in0 + sidx * d.src_stride;
-        const R* meta = reinterpret_cast<const R*>(src - meta_bytes);
-        const uint64_t value = load_bytes(src + g * BITS, BITS);
-        uint32_t u0 = 0, m0 = 0;
-        if (oneb) load_meta_pair<R>(meta, bk0, u0, m0);
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-          uint32_t ur = u0, mr = m0;
-          if (!oneb) {
-            const int64_t bk = (g * 8 + j) / d.bucket;
-            load_meta_pair<R>(meta, bk, ur, mr);
-          }
-          accum_raw<T>(v[j], !have && sidx == 0,
-                       decode_raw<T>(ur, mr, pack_level<BITS>(value, j)));
-        }
-      }
-      store8<T>(outp, al16, v);
-    }
-
-  tail16:
-    // tail group (fewer than 8 elements): one thread, scalar
-    const int mtail = static_cast<int>(nq - full_groups * 8);
-    if (mtail > 0 && t0 == 0) {
-      const int64_t g = full_groups;
-      const int nbytes = static_cast<int>(
-          min(static_cast<int64_t>(BITS), sg.packed_bytes - g * BITS));
-      R* outp = reinterpret_cast<R*>(d.out) + g * 8;
-      for (int sidx = 0; sidx < d.nsrc; sidx++) {
-        const uint8_t* src = in0 + sidx * d.src_stride;
-        const R* meta = reinterpret_cast<const R*>(src - meta_bytes);
-        const uint64_t value = load_bytes(src + g * BITS, nbytes);
-        for (int j = 0; j < mtail; j++) {
-          const int64_t bk = (g * 8 + j) / d.bucket;
-          const bool first = sidx == 0 && !d.add;
-          uint32_t v = first ? 0 : outp[j];
-          accum_raw<T>(v, first,
-                       decode_raw<T>(meta[2 * bk], meta[2 * bk + 1],
-                                     pack_level<BITS>(value, j)));
-          outp[j] = static_cast<R>(v);
-        }
-      }
-    }
+    const int mtail = static_cast<int>(sg.nq - full_units * E);
+    if (mtail > 0 && t0 == 0)
+      decode_unit<T, BITS>(d, sg, al16, full_units, mtail);
   }
 }
 

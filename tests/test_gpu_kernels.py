@@ -17,6 +17,7 @@ CASES = [  # (n, bucket)
     (5000, 120),       # bucket % 8 == 0 small
     (9, 7),            # tiny, bucket % 8 != 0
     (100000, 8192),    # bucket > register stash capacity
+    (1003, 50),        # decode units straddle buckets; ragged n % 8 == 3
 ]
 
 
@@ -65,7 +66,7 @@ def _add_in_T(base, dec):
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("bits", [1, 3, 4, 8])
 @pytest.mark.parametrize("n,bucket", [(520, 512), (1000, 64), (4100, 4096),
-                                      (9, 7)])
+                                      (9, 7), (1003, 50)])
 def test_unaligned_base_matches_golden(dtype, bits, n, bucket):
     """Input and output one element past a 16B boundary: the whole slice
     goes through the generic quantize kernel, and decode takes the
@@ -115,6 +116,10 @@ def test_dequantize_add_accumulates_in_T(dtype):
     pytest.param(3, 8192, 512, torch.float16, id="3-8192-512-fp16"),
     pytest.param(3, 1001, 64, torch.bfloat16, id="3-1001-64-bf16"),
     pytest.param(3, 8192, 512, torch.bfloat16, id="3-8192-512-bf16"),
+    # bucket % 8 != 0: multi-source accumulate through the generic kernel's
+    # full-unit loop
+    pytest.param(3, 1001, 100, torch.float32, id="3-1001-100-fp32"),
+    pytest.param(3, 1001, 100, torch.float16, id="3-1001-100-fp16"),
 ])
 def test_dequantize_multi_matches_sequential(nsrc, n, bucket, dtype):
     from torch_cgx_amd import _C
@@ -261,7 +266,8 @@ def test_skip_incomplete_dequant_add():
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("bits", [2, 4, 8])
 @pytest.mark.parametrize("n,bucket", [(4096, 512), (1000, 512), (131, 64),
-                                      (4096, 1024), (520, 512)])
+                                      (4096, 1024), (520, 512),
+                                      (1000, 1024)])
 def test_error_feedback_matches_golden(dtype, bits, n, bucket):
     _check_error_feedback(dtype, bits, n, bucket, offset=0)
 

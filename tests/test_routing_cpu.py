@@ -158,6 +158,7 @@ QUANT_ROWS = {
     (5000, 120): [(FAST, [0, 41], [0]), (GENERIC, [0, 1], [TAIL])],
     (9, 7): [(TWO_PASS, [0, 2], [0])],
     (100000, 8192): [(GENERIC, [0, 13], [0])],
+    (1003, 50): [(TWO_PASS, [0, 21], [0])],
 }
 
 
@@ -299,6 +300,7 @@ DEQUANT_ROWS = {
     (5000, 120): ([_F(5000)], [_F(5000)]),
     (9, 7): ([(GENERIC, 2, [0])], [(GENERIC, 2, [0])]),
     (100000, 8192): ([_F(100000)], [_F(100000)]),
+    (1003, 50): ([(GENERIC, 126, [0])], [(GENERIC, 126, [0])]),
 }
 
 
