@@ -19,6 +19,7 @@
 #include <tuple>
 
 #include "backend.h"
+#include "bn_plan.h"
 #include "reducer.h"
 
 namespace cgx {
@@ -426,6 +427,179 @@ py::tuple py_plan_chunk(const std::vector<PyView>& views, at::ScalarType st,
   return py::make_tuple(pl.offs, pl.szs, pl.comp, rs);
 }
 
+// ---- fused BatchNorm (bn_plan.h, bn_kernels.hip) ---------------------------
+
+// What the kernels index: a dense channels_last bf16 CUDA tensor whose first
+// byte is 16-byte aligned.
+bool bn_tensor_ok(const at::Tensor& t) {
+  return t.is_cuda() && t.scalar_type() == at::kBFloat16 && t.dim() == 4 &&
+         t.numel() > 0 && t.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+         reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
+BnPlan bn_plan_of(const at::Tensor& t) {
+  return bn_plan(t.numel() / t.size(1), t.size(1));
+}
+
+bool py_bn_eligible(const at::Tensor& x) {
+  return bn_tensor_ok(x) && bn_plan_of(x).eligible;
+}
+
+float* bn_channel_vec(const at::Tensor& t, int64_t c, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat &&
+                  t.is_contiguous() && t.numel() == c,
+              "bn_act: ", what, " must be a contiguous fp32 CUDA vector of ",
+              c, " elements");
+  return t.data_ptr<float>();
+}
+
+at::Tensor bn_workspace(const BnPlan& p, const at::Tensor& like) {
+  return at::empty({2 * p.partial_floats + p.grid},
+                   like.options().dtype(at::kFloat));
+}
+
+// -> (out, mean, invstd, mask | None); running statistics updated in place
+std::tuple<at::Tensor, at::Tensor, at::Tensor, c10::optional<at::Tensor>>
+py_bn_act_forward(const at::Tensor& x, const c10::optional<at::Tensor>& identity,
+                  const at::Tensor& weight, const at::Tensor& bias,
+                  at::Tensor running_mean, at::Tensor running_var,
+                  double momentum, double eps, bool relu) {
+  TORCH_CHECK(py_bn_eligible(x), "bn_act_forward: input is not eligible");
+  const BnPlan p = bn_plan_of(x);
+  const int64_t c = p.channels;
+  if (identity.has_value())
+    TORCH_CHECK(bn_tensor_ok(*identity) && identity->sizes() == x.sizes() &&
+                    identity->device() == x.device(),
+                "bn_act_forward: identity must match the input");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device().index());
+  auto out = at::empty(x.sizes(), x.options(), at::MemoryFormat::ChannelsLast);
+  auto stats = x.options().dtype(at::kFloat);
+  auto mean = at::empty({c}, stats), invstd = at::empty({c}, stats);
+  c10::optional<at::Tensor> mask;
+  if (relu) mask = at::empty({x.numel() / 8}, x.options().dtype(at::kByte));
+  auto part = bn_workspace(p, x);
+  BnForwardArgs a;
+  a.x = x.data_ptr();
+  a.identity = identity.has_value() ? identity->data_ptr() : nullptr;
+  a.weight = bn_channel_vec(weight, c, "weight");
+  a.bias = bn_channel_vec(bias, c, "bias");
+  a.running_mean = bn_channel_vec(running_mean, c, "running_mean");
+  a.running_var = bn_channel_vec(running_var, c, "running_var");
+  a.momentum = (float)momentum;
+  a.eps = (float)eps;
+  a.relu = relu;
+  a.out = out.data_ptr();
+  a.mean = mean.data_ptr<float>();
+  a.invstd = invstd.data_ptr<float>();
+  a.mask = relu ? mask->data_ptr<uint8_t>() : nullptr;
+  a.part = part.data_ptr<float>();
+  launch_bn_forward(
+      p, a, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(
+                x.device().index()).stream());
+  return {out, mean, invstd, mask};
+}
+
+// -> (dx, dgamma, dbeta, didentity | None).  Without a mask the identity
+// branch's gradient is dy itself and is returned as such.
+std::tuple<at::Tensor, at::Tensor, at::Tensor, c10::optional<at::Tensor>>
+py_bn_act_backward(at::Tensor dy, const at::Tensor& x, const at::Tensor& mean,
+                   const at::Tensor& invstd, const at::Tensor& weight,
+                   const c10::optional<at::Tensor>& mask, bool has_identity) {
+  TORCH_CHECK(py_bn_eligible(x), "bn_act_backward: input is not eligible");
+  const BnPlan p = bn_plan_of(x);
+  const int64_t c = p.channels;
+  TORCH_CHECK(dy.is_cuda() && dy.device() == x.device() &&
+                  dy.scalar_type() == at::kBFloat16 && dy.sizes() == x.sizes(),
+              "bn_act_backward: dy must match the input");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device().index());
+  if (!bn_tensor_ok(dy)) dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
+  if (!bn_tensor_ok(dy)) dy = dy.clone(at::MemoryFormat::ChannelsLast);
+  if (mask.has_value())
+    TORCH_CHECK(mask->is_cuda() && mask->scalar_type() == at::kByte &&
+                    mask->is_contiguous() && mask->numel() == x.numel() / 8,
+                "bn_act_backward: mask must hold one bit per element");
+  auto dx = at::empty(x.sizes(), x.options(), at::MemoryFormat::ChannelsLast);
+  auto stats = x.options().dtype(at::kFloat);
+  auto dgamma = at::empty({c}, stats), dbeta = at::empty({c}, stats);
+  c10::optional<at::Tensor> didentity;
+  if (has_identity)
+    didentity = mask.has_value()
+                    ? at::empty(x.sizes(), x.options(),
+                                at::MemoryFormat::ChannelsLast)
+                    : dy;
+  auto part = bn_workspace(p, x);
+  BnBackwardArgs a;
+  a.dy = dy.data_ptr();
+  a.x = x.data_ptr();
+  a.mean = bn_channel_vec(mean, c, "mean");
+  a.invstd = bn_channel_vec(invstd, c, "invstd");
+  a.weight = bn_channel_vec(weight, c, "weight");
+  a.mask = mask.has_value() ? mask->data_ptr<uint8_t>() : nullptr;
+  a.dx = dx.data_ptr();
+  a.didentity =
+      has_identity && mask.has_value() ? didentity->data_ptr() : nullptr;
+  a.dgamma = dgamma.data_ptr<float>();
+  a.dbeta = dbeta.data_ptr<float>();
+  a.part = part.data_ptr<float>();
+  launch_bn_backward(
+      p, a, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(
+                x.device().index()).stream());
+  return {dx, dgamma, dbeta, didentity};
+}
+
+py::dict py_bn_plan(int64_t rows, int64_t channels) {
+  const BnPlan p = bn_plan(rows, channels);
+  py::dict d;
+  d["eligible"] = p.eligible;
+  d["threads"] = kBnThreads;
+  d["cgs"] = p.cgs;
+  d["tile_cgs"] = p.tc;
+  d["ctiles"] = p.ctiles;
+  d["rows_per_iter"] = p.rln;
+  d["splits"] = p.splits;
+  d["grid"] = p.grid;
+  d["rows_per_thread"] = p.rows_per_thread;
+  d["partial_floats"] = p.partial_floats;
+  return d;
+}
+
+// Test seam: replay the kernels' sweep on the host.  Row t of the result is
+// thread t % 256 of workgroup t / 256: the vector indices it visits in order,
+// -1 once it has run out of rows.
+at::Tensor py_bn_sweep_indices(int64_t rows, int64_t channels) {
+  const BnPlan p = bn_plan(rows, channels);
+  TORCH_CHECK(p.eligible, "bn_sweep_indices: shape is not eligible");
+  auto out = at::full({(int64_t)p.grid * kBnThreads, p.rows_per_thread + 1},
+                      -1, at::TensorOptions().dtype(at::kLong));
+  int64_t* o = out.data_ptr<int64_t>();
+  const int64_t width = p.rows_per_thread + 1;
+  for (int wg = 0; wg < p.grid; wg++)
+    for (int tid = 0; tid < kBnThreads; tid++) {
+      const BnSweep sw = bn_sweep(p, wg, tid);
+      int64_t k = 0;
+      for (int64_t r = sw.row; r < p.rows; r += sw.stride, k++) {
+        TORCH_CHECK(k < width, "bn_sweep_indices: run longer than planned");
+        o[((int64_t)wg * kBnThreads + tid) * width + k] = bn_vec(p, r, sw.cg);
+      }
+    }
+  return out;
+}
+
+// Test seam: the partial-buffer offsets workgroup `wg` writes (per reduction),
+// as the kernels compute them.
+std::vector<int64_t> py_bn_partial_offsets(int64_t rows, int64_t channels,
+                                           int wg) {
+  const BnPlan p = bn_plan(rows, channels);
+  TORCH_CHECK(p.eligible && wg >= 0 && wg < p.grid, "bn_partial_offsets: bad");
+  std::vector<int64_t> offs;
+  for (int tid = 0; tid < p.tc; tid++) {
+    const BnSweep sw = bn_sweep(p, wg, tid);
+    const int64_t o = bn_partial_offset(p, wg, sw.cg);
+    for (int j = 0; j < 8; j++) offs.push_back(o + j);
+  }
+  return offs;
+}
+
 void py_register_layer(int64_t bucket_idx, int64_t layer_idx, int64_t numel,
                        int64_t bits, int64_t bucket_size) {
   Registry::get().register_layer((int)bucket_idx, (int)layer_idx, numel,
@@ -575,6 +749,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Test seam: the launch router's dequantize plan for "
         "[(in, out, n, bits, bucket, skip_incomplete)] -> "
         "[(bits, kind, descs, total_groups, any_residual)].");
+  m.def("bn_act_forward", &cgx::py_bn_act_forward, py::arg("x"),
+        py::arg("identity"), py::arg("weight"), py::arg("bias"),
+        py::arg("running_mean"), py::arg("running_var"), py::arg("momentum"),
+        py::arg("eps"), py::arg("relu"),
+        "Training-mode BatchNorm2d of a channels_last bf16 tensor, fused with "
+        "an optional residual add and ReLU -> (out, mean, invstd, mask | "
+        "None); updates the running statistics in place.");
+  m.def("bn_act_backward", &cgx::py_bn_act_backward, py::arg("dy"),
+        py::arg("x"), py::arg("mean"), py::arg("invstd"), py::arg("weight"),
+        py::arg("mask"), py::arg("has_identity"),
+        "Backward of bn_act_forward -> (dx, dgamma, dbeta, didentity | None).");
+  m.def("bn_eligible", &cgx::py_bn_eligible, py::arg("x"),
+        "True where the fused BatchNorm kernels take `x`: CUDA, bf16, dense "
+        "channels_last, and a shape bn_plan calls eligible.");
+  m.def("bn_plan", &cgx::py_bn_plan, py::arg("rows"), py::arg("channels"),
+        "Test seam: the launch geometry of the fused BatchNorm kernels for a "
+        "[rows, channels] activation.");
+  m.def("bn_sweep_indices", &cgx::py_bn_sweep_indices, py::arg("rows"),
+        py::arg("channels"),
+        "Test seam: [grid*threads, rows_per_thread+1] int64, the 16-byte "
+        "vector indices every thread visits (-1: none).");
+  m.def("bn_partial_offsets", &cgx::py_bn_partial_offsets, py::arg("rows"),
+        py::arg("channels"), py::arg("wg"),
+        "Test seam: the partial-buffer floats workgroup `wg` writes.");
   m.attr("FLAG_SKIP_INCOMPLETE") = cgx::kFlagSkipIncomplete;
   m.attr("FLAG_TAIL_ONLY") = cgx::kFlagTailOnly;
   m.attr("KIND_FAST") = (int)cgx::kFast;

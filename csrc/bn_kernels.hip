@@ -1,0 +1,511 @@
+// Training-mode BatchNorm2d on a channels_last bf16 activation, fused with the
+// ReLU and the residual add that follow it in a ResNet bottleneck.
+//
+// The activation is a dense [R, C] matrix (R = N*H*W); parameters and
+// statistics are fp32.  Every thread handles one 16-byte vector (8 channels of
+// one row) per iteration and keeps its channel group for the whole sweep
+// (geometry: bn_plan.h), so per-channel values live in registers.
+//
+//   forward   bn_stats          per-thread Welford over its rows, Chan merge
+//                               across the workgroup through LDS, one
+//                               (mean, M2) partial per (split, channel)
+//             bn_stats_finalize fixed-order Chan merge of the partials ->
+//                               mean, invstd, running statistics
+//             bn_apply          y = ((x-mean)*invstd)*gamma + beta -> bf16,
+//                               [+ identity -> bf16], [ReLU + 1 mask bit]
+//   backward  bn_bwd_reduce     per-channel sum(g), sum(g*xhat), g = dy under
+//                               the mask
+//             bn_bwd_finalize   fixed-order sum of the partials -> dbeta,
+//                               dgamma
+//             bn_bwd_dx         dx = gamma*invstd*(g - sum(g)/R
+//                                                    - xhat*sum(g*xhat)/R),
+//                               [masked dy for the identity branch]
+//
+// No atomics anywhere: every reduction has a fixed order, so results are
+// bitwise reproducible.  Compiled with -ffp-contract=off; the fused
+// multiply-adds below are explicit.
+#include <hip/hip_runtime.h>
+
+#include "bn_plan.h"
+#include "check.h"
+
+namespace cgx {
+namespace {
+
+constexpr int kT = kBnThreads;
+
+__device__ inline void unpack8(const uint4& v, float (&f)[8]) {
+  f[0] = __uint_as_float(v.x << 16);
+  f[1] = __uint_as_float(v.x & 0xffff0000u);
+  f[2] = __uint_as_float(v.y << 16);
+  f[3] = __uint_as_float(v.y & 0xffff0000u);
+  f[4] = __uint_as_float(v.z << 16);
+  f[5] = __uint_as_float(v.z & 0xffff0000u);
+  f[6] = __uint_as_float(v.w << 16);
+  f[7] = __uint_as_float(v.w & 0xffff0000u);
+}
+
+// fp32 -> bf16 bits, round to nearest even; NaN stays a (quiet) NaN
+__device__ inline unsigned bf16_bits(float f) {
+  const unsigned u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
+  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+
+__device__ inline uint4 pack8(const unsigned (&b)[8]) {
+  return make_uint4(b[0] | (b[1] << 16), b[2] | (b[3] << 16),
+                    b[4] | (b[5] << 16), b[6] | (b[7] << 16));
+}
+
+__device__ inline unsigned half_of(const uint4& v, int j) {
+  const unsigned w = j < 2 ? v.x : j < 4 ? v.y : j < 6 ? v.z : v.w;
+  return (j & 1) ? w >> 16 : w & 0xffffu;
+}
+
+template <int K>
+__device__ inline void load_k(float (&dst)[K], const float* src) {
+#pragma unroll
+  for (int j = 0; j < K; j++) dst[j] = src[j];
+}
+
+// ---- running (count, mean, M2) over K channels that share one count --------
+
+template <int K>
+struct Moments {
+  float n = 0.f;
+  float mean[K] = {};
+  float m2[K] = {};
+
+  // Welford step; the count, hence 1/n, is shared by the K channels
+  __device__ void push(const float (&x)[K]) {
+    n += 1.f;
+    const float inv = __builtin_amdgcn_rcpf(n);
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      const float d = x[j] - mean[j];
+      mean[j] = fmaf(d, inv, mean[j]);
+      m2[j] = fmaf(d, x[j] - mean[j], m2[j]);
+    }
+  }
+
+  // Chan et al. merge of another run; either side may be empty
+  __device__ void merge(float nb, const float (&mb)[K], const float (&m2b)[K]) {
+    const float nt = n + nb;
+    const float fb = nt > 0.f ? nb / nt : 0.f;
+    const float w = n * fb;
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      const float d = mb[j] - mean[j];
+      mean[j] = fmaf(d, fb, mean[j]);
+      m2[j] = (m2[j] + m2b[j]) + (d * d) * w;
+    }
+    n = nt;
+  }
+};
+
+// Tree merge across the threads tid, tid+lo, tid+2*lo, ... of a workgroup (lo
+// a power of two); threads below `lo` end up with the result.
+template <int K>
+__device__ inline void wg_merge(Moments<K>& m, float (*sh)[kT], int tid,
+                                int lo) {
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    sh[j][tid] = m.mean[j];
+    sh[K + j][tid] = m.m2[j];
+  }
+  sh[2 * K][tid] = m.n;
+  __syncthreads();
+  for (int h = kT / 2; h >= lo; h >>= 1) {
+    if (tid < h) {
+      float mb[K], m2b[K];
+#pragma unroll
+      for (int j = 0; j < K; j++) {
+        mb[j] = sh[j][tid + h];
+        m2b[j] = sh[K + j][tid + h];
+      }
+      m.merge(sh[2 * K][tid + h], mb, m2b);
+#pragma unroll
+      for (int j = 0; j < K; j++) {
+        sh[j][tid] = m.mean[j];
+        sh[K + j][tid] = m.m2[j];
+      }
+      sh[2 * K][tid] = m.n;
+    }
+    __syncthreads();
+  }
+}
+
+// Same for K plain sums.
+template <int K>
+__device__ inline void wg_sum(float (&s)[K], float (*sh)[kT], int tid, int lo) {
+#pragma unroll
+  for (int j = 0; j < K; j++) sh[j][tid] = s[j];
+  __syncthreads();
+  for (int h = kT / 2; h >= lo; h >>= 1) {
+    if (tid < h) {
+#pragma unroll
+      for (int j = 0; j < K; j++) {
+        s[j] += sh[j][tid + h];
+        sh[j][tid] = s[j];
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// ---- forward ---------------------------------------------------------------
+
+__global__ __launch_bounds__(kT) void bn_stats(const uint4* __restrict__ x,
+                                               float* __restrict__ pmean,
+                                               float* __restrict__ pm2,
+                                               float* __restrict__ pcnt,
+                                               BnPlan p) {
+  __shared__ float sh[17][kT];
+  const int tid = threadIdx.x;
+  const BnSweep sw = bn_sweep(p, blockIdx.x, tid);
+  Moments<8> m;
+  float f[8];
+  int64_t r = sw.row;
+  // four independent loads in flight per thread
+  for (; r + 3 * sw.stride < p.rows; r += 4 * sw.stride) {
+    const uint4 v0 = x[bn_vec(p, r, sw.cg)];
+    const uint4 v1 = x[bn_vec(p, r + sw.stride, sw.cg)];
+    const uint4 v2 = x[bn_vec(p, r + 2 * sw.stride, sw.cg)];
+    const uint4 v3 = x[bn_vec(p, r + 3 * sw.stride, sw.cg)];
+    unpack8(v0, f);
+    m.push(f);
+    unpack8(v1, f);
+    m.push(f);
+    unpack8(v2, f);
+    m.push(f);
+    unpack8(v3, f);
+    m.push(f);
+  }
+  for (; r < p.rows; r += sw.stride) {
+    unpack8(x[bn_vec(p, r, sw.cg)], f);
+    m.push(f);
+  }
+  wg_merge<8>(m, sh, tid, p.tc);
+  if (tid < p.tc) {
+    const int64_t o = bn_partial_offset(p, blockIdx.x, sw.cg);
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      pmean[o + j] = m.mean[j];
+      pm2[o + j] = m.m2[j];
+    }
+    if (tid == 0) pcnt[blockIdx.x] = m.n;
+  }
+}
+
+// kBnFinChannels channels per workgroup, kFinLanes lanes per channel: lane l
+// merges splits l, l+kFinLanes, ... in order (four loads in flight), then the
+// lanes merge as a tree.
+constexpr int kFinLanes = kT / kBnFinChannels;
+
+__global__ __launch_bounds__(kT) void bn_stats_finalize(
+    const float* __restrict__ pmean, const float* __restrict__ pm2,
+    const float* __restrict__ pcnt, float* __restrict__ mean,
+    float* __restrict__ invstd, float* __restrict__ running_mean,
+    float* __restrict__ running_var, float momentum, float eps, BnPlan p) {
+  __shared__ float sh[3][kT];
+  const int tid = threadIdx.x;
+  const int c = blockIdx.x * kBnFinChannels + tid % kBnFinChannels;
+  const int lane = tid / kBnFinChannels;
+  Moments<1> m;
+  if (c < p.channels) {
+    const int ct = (c / 8) / p.tc;
+    for (int s0 = lane; s0 < p.splits; s0 += 4 * kFinLanes) {
+      float nb[4], mb[4][1], m2b[4][1];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int s = s0 + u * kFinLanes;
+        const bool live = s < p.splits;
+        const int64_t o = (int64_t)s * p.channels + c;
+        nb[u] = live ? pcnt[s * p.ctiles + ct] : 0.f;
+        mb[u][0] = live ? pmean[o] : 0.f;
+        m2b[u][0] = live ? pm2[o] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; u++) m.merge(nb[u], mb[u], m2b[u]);
+    }
+  }
+  wg_merge<1>(m, sh, tid, kBnFinChannels);
+  if (tid < kBnFinChannels && c < p.channels) {
+    const float var = m.m2[0] / m.n;
+    mean[c] = m.mean[0];
+    invstd[c] = 1.f / sqrtf(var + eps);
+    running_mean[c] =
+        (1.f - momentum) * running_mean[c] + momentum * m.mean[0];
+    running_var[c] =
+        (1.f - momentum) * running_var[c] + momentum * (m.m2[0] / (m.n - 1.f));
+  }
+}
+
+template <bool RELU, bool ADD>
+__device__ inline void apply_one(const uint4& xv, const uint4& iv,
+                                 const float (&mean)[8],
+                                 const float (&invstd)[8],
+                                 const float (&gamma)[8],
+                                 const float (&beta)[8], uint4* out,
+                                 uint8_t* mask, int64_t i) {
+  float x[8], idn[8];
+  unpack8(xv, x);
+  if (ADD) unpack8(iv, idn);
+  unsigned o[8], mbits = 0;
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    float y = ((x[j] - mean[j]) * invstd[j]) * gamma[j] + beta[j];
+    unsigned b = bf16_bits(y);
+    if (ADD) {
+      // the unfused graph rounds the BN output to bf16 before the add
+      y = __uint_as_float(b << 16) + idn[j];
+      b = bf16_bits(y);
+    }
+    if (RELU) {
+      // like clamp_min: a NaN stays; like threshold_backward: its gradient
+      // passes (the bit is clear only where the output is <= 0)
+      const float z = __uint_as_float(b << 16);
+      if (z <= 0.f) b = 0;
+      else mbits |= 1u << j;
+    }
+    o[j] = b;
+  }
+  out[i] = pack8(o);
+  if (RELU) mask[i] = (uint8_t)mbits;
+}
+
+template <bool RELU, bool ADD>
+__global__ __launch_bounds__(kT) void bn_apply(
+    const uint4* __restrict__ x, const uint4* __restrict__ identity,
+    const float* __restrict__ mean_, const float* __restrict__ invstd_,
+    const float* __restrict__ weight, const float* __restrict__ bias,
+    uint4* __restrict__ out, uint8_t* __restrict__ mask, BnPlan p) {
+  const BnSweep sw = bn_sweep(p, blockIdx.x, threadIdx.x);
+  float mean[8], invstd[8], gamma[8], beta[8];
+  load_k(mean, mean_ + sw.cg * 8);
+  load_k(invstd, invstd_ + sw.cg * 8);
+  load_k(gamma, weight + sw.cg * 8);
+  load_k(beta, bias + sw.cg * 8);
+  const uint4 none = make_uint4(0, 0, 0, 0);
+  int64_t r = sw.row;
+  for (; r + sw.stride < p.rows; r += 2 * sw.stride) {
+    const int64_t i0 = bn_vec(p, r, sw.cg);
+    const int64_t i1 = bn_vec(p, r + sw.stride, sw.cg);
+    const uint4 x0 = x[i0], x1 = x[i1];
+    const uint4 d0 = ADD ? identity[i0] : none, d1 = ADD ? identity[i1] : none;
+    apply_one<RELU, ADD>(x0, d0, mean, invstd, gamma, beta, out, mask, i0);
+    apply_one<RELU, ADD>(x1, d1, mean, invstd, gamma, beta, out, mask, i1);
+  }
+  if (r < p.rows) {
+    const int64_t i0 = bn_vec(p, r, sw.cg);
+    apply_one<RELU, ADD>(x[i0], ADD ? identity[i0] : none, mean, invstd, gamma,
+                         beta, out, mask, i0);
+  }
+}
+
+// ---- backward --------------------------------------------------------------
+
+// g = dy where the mask bit is set, +0 elsewhere; returned as bf16 bits too.
+template <bool RELU>
+__device__ inline void masked_dy(const uint4& dyv, unsigned mbits,
+                                 float (&g)[8], unsigned (&gb)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    gb[j] = half_of(dyv, j);
+    if (RELU && !((mbits >> j) & 1u)) gb[j] = 0;
+    g[j] = __uint_as_float(gb[j] << 16);
+  }
+}
+
+template <bool RELU>
+__global__ __launch_bounds__(kT) void bn_bwd_reduce(
+    const uint4* __restrict__ dy, const uint4* __restrict__ x,
+    const uint8_t* __restrict__ mask, const float* __restrict__ mean_,
+    const float* __restrict__ invstd_, float* __restrict__ psg,
+    float* __restrict__ psgx, BnPlan p) {
+  __shared__ float sh[16][kT];
+  const int tid = threadIdx.x;
+  const BnSweep sw = bn_sweep(p, blockIdx.x, tid);
+  float mean[8], invstd[8];
+  load_k(mean, mean_ + sw.cg * 8);
+  load_k(invstd, invstd_ + sw.cg * 8);
+  float s[16] = {};  // sum(g) in 0..7, sum(g*xhat) in 8..15
+  auto accumulate = [&](const uint4& dyv, const uint4& xv, unsigned mbits) {
+    float g[8], xf[8];
+    unsigned gb[8];
+    masked_dy<RELU>(dyv, mbits, g, gb);
+    unpack8(xv, xf);
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const float xhat = (xf[j] - mean[j]) * invstd[j];
+      s[j] += g[j];
+      s[8 + j] = fmaf(g[j], xhat, s[8 + j]);
+    }
+  };
+  int64_t r = sw.row;
+  for (; r + sw.stride < p.rows; r += 2 * sw.stride) {
+    const int64_t i0 = bn_vec(p, r, sw.cg);
+    const int64_t i1 = bn_vec(p, r + sw.stride, sw.cg);
+    const uint4 a0 = dy[i0], a1 = dy[i1];
+    const uint4 b0 = x[i0], b1 = x[i1];
+    const unsigned m0 = RELU ? mask[i0] : 0xffu, m1 = RELU ? mask[i1] : 0xffu;
+    accumulate(a0, b0, m0);
+    accumulate(a1, b1, m1);
+  }
+  if (r < p.rows) {
+    const int64_t i0 = bn_vec(p, r, sw.cg);
+    accumulate(dy[i0], x[i0], RELU ? mask[i0] : 0xffu);
+  }
+  wg_sum<16>(s, sh, tid, p.tc);
+  if (tid < p.tc) {
+    const int64_t o = bn_partial_offset(p, blockIdx.x, sw.cg);
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      psg[o + j] = s[j];
+      psgx[o + j] = s[8 + j];
+    }
+  }
+}
+
+__global__ __launch_bounds__(kT) void bn_bwd_finalize(
+    const float* __restrict__ psg, const float* __restrict__ psgx,
+    float* __restrict__ dbeta, float* __restrict__ dgamma, BnPlan p) {
+  __shared__ float sh[2][kT];
+  const int tid = threadIdx.x;
+  const int c = blockIdx.x * kBnFinChannels + tid % kBnFinChannels;
+  const int lane = tid / kBnFinChannels;
+  float s[2] = {0.f, 0.f};
+  if (c < p.channels) {
+    for (int s0 = lane; s0 < p.splits; s0 += 4 * kFinLanes) {
+      float a[4], b[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int sp = s0 + u * kFinLanes;
+        const bool live = sp < p.splits;
+        const int64_t o = (int64_t)sp * p.channels + c;
+        a[u] = live ? psg[o] : 0.f;
+        b[u] = live ? psgx[o] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        s[0] += a[u];
+        s[1] += b[u];
+      }
+    }
+  }
+  wg_sum<2>(s, sh, tid, kBnFinChannels);
+  if (tid < kBnFinChannels && c < p.channels) {
+    dbeta[c] = s[0];
+    dgamma[c] = s[1];
+  }
+}
+
+template <bool RELU, bool ADD>
+__global__ __launch_bounds__(kT) void bn_bwd_dx(
+    const uint4* __restrict__ dy, const uint4* __restrict__ x,
+    const uint8_t* __restrict__ mask, const float* __restrict__ mean_,
+    const float* __restrict__ invstd_, const float* __restrict__ weight,
+    const float* __restrict__ dbeta, const float* __restrict__ dgamma,
+    uint4* __restrict__ dx, uint4* __restrict__ didentity, BnPlan p) {
+  const BnSweep sw = bn_sweep(p, blockIdx.x, threadIdx.x);
+  float mean[8], invstd[8], scale[8], mg[8], mgx[8];
+  load_k(mean, mean_ + sw.cg * 8);
+  load_k(invstd, invstd_ + sw.cg * 8);
+  load_k(scale, weight + sw.cg * 8);
+  load_k(mg, dbeta + sw.cg * 8);
+  load_k(mgx, dgamma + sw.cg * 8);
+  const float inv_r = 1.f / (float)p.rows;
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    scale[j] *= invstd[j];
+    mg[j] *= inv_r;
+    mgx[j] *= inv_r;
+  }
+  auto one = [&](const uint4& dyv, const uint4& xv, unsigned mbits, int64_t i) {
+    float g[8], xf[8];
+    unsigned gb[8], o[8];
+    masked_dy<RELU>(dyv, mbits, g, gb);
+    unpack8(xv, xf);
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const float xhat = (xf[j] - mean[j]) * invstd[j];
+      o[j] = bf16_bits(scale[j] * ((g[j] - mg[j]) - xhat * mgx[j]));
+    }
+    dx[i] = pack8(o);
+    if (ADD) didentity[i] = pack8(gb);
+  };
+  int64_t r = sw.row;
+  for (; r + sw.stride < p.rows; r += 2 * sw.stride) {
+    const int64_t i0 = bn_vec(p, r, sw.cg);
+    const int64_t i1 = bn_vec(p, r + sw.stride, sw.cg);
+    const uint4 a0 = dy[i0], a1 = dy[i1];
+    const uint4 b0 = x[i0], b1 = x[i1];
+    const unsigned m0 = RELU ? mask[i0] : 0xffu, m1 = RELU ? mask[i1] : 0xffu;
+    one(a0, b0, m0, i0);
+    one(a1, b1, m1, i1);
+  }
+  if (r < p.rows) {
+    const int64_t i0 = bn_vec(p, r, sw.cg);
+    one(dy[i0], x[i0], RELU ? mask[i0] : 0xffu, i0);
+  }
+}
+
+int fin_grid(const BnPlan& p) {
+  return (p.channels + kBnFinChannels - 1) / kBnFinChannels;
+}
+
+}  // namespace
+
+void launch_bn_forward(const BnPlan& p, const BnForwardArgs& a,
+                       hipStream_t stream) {
+  float* pmean = a.part;
+  float* pm2 = a.part + p.partial_floats;
+  float* pcnt = a.part + 2 * p.partial_floats;
+  const uint4* x = static_cast<const uint4*>(a.x);
+  const uint4* idn = static_cast<const uint4*>(a.identity);
+  uint4* out = static_cast<uint4*>(a.out);
+  const dim3 grid(p.grid), block(kT);
+  hipLaunchKernelGGL(bn_stats, grid, block, 0, stream, x, pmean, pm2, pcnt, p);
+  hipLaunchKernelGGL(bn_stats_finalize, dim3(fin_grid(p)), block, 0, stream,
+                     pmean, pm2, pcnt, a.mean, a.invstd, a.running_mean,
+                     a.running_var, a.momentum, a.eps, p);
+#define CGX_BN_APPLY(RELU, ADD)                                              \
+  hipLaunchKernelGGL((bn_apply<RELU, ADD>), grid, block, 0, stream, x, idn,  \
+                     a.mean, a.invstd, a.weight, a.bias, out, a.mask, p)
+  if (a.relu && idn) CGX_BN_APPLY(true, true);
+  else if (a.relu) CGX_BN_APPLY(true, false);
+  else if (idn) CGX_BN_APPLY(false, true);
+  else CGX_BN_APPLY(false, false);
+#undef CGX_BN_APPLY
+  CGX_HIP_CHECK(hipGetLastError());
+}
+
+void launch_bn_backward(const BnPlan& p, const BnBackwardArgs& a,
+                        hipStream_t stream) {
+  float* psg = a.part;
+  float* psgx = a.part + p.partial_floats;
+  const uint4* dy = static_cast<const uint4*>(a.dy);
+  const uint4* x = static_cast<const uint4*>(a.x);
+  uint4* dx = static_cast<uint4*>(a.dx);
+  uint4* did = static_cast<uint4*>(a.didentity);
+  const dim3 grid(p.grid), block(kT);
+  if (a.mask)
+    hipLaunchKernelGGL(bn_bwd_reduce<true>, grid, block, 0, stream, dy, x,
+                       a.mask, a.mean, a.invstd, psg, psgx, p);
+  else
+    hipLaunchKernelGGL(bn_bwd_reduce<false>, grid, block, 0, stream, dy, x,
+                       a.mask, a.mean, a.invstd, psg, psgx, p);
+  hipLaunchKernelGGL(bn_bwd_finalize, dim3(fin_grid(p)), block, 0, stream, psg,
+                     psgx, a.dbeta, a.dgamma, p);
+#define CGX_BN_DX(RELU, ADD)                                                 \
+  hipLaunchKernelGGL((bn_bwd_dx<RELU, ADD>), grid, block, 0, stream, dy, x,  \
+                     a.mask, a.mean, a.invstd, a.weight, a.dbeta, a.dgamma,  \
+                     dx, did, p)
+  if (a.mask && did) CGX_BN_DX(true, true);
+  else if (a.mask) CGX_BN_DX(true, false);
+  else CGX_BN_DX(false, false);
+#undef CGX_BN_DX
+  CGX_HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace cgx

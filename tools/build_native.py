@@ -16,10 +16,12 @@ from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SOURCES = [
     "csrc/quant_kernels.hip",
+    "csrc/bn_kernels.hip",
     "csrc/compress.cc",
     "csrc/config.cc",
     "csrc/registry.cc",
     "csrc/plan.cc",
+    "csrc/bn_plan.cc",
     "csrc/phase_timer.cc",
     "csrc/engine.cc",
     "csrc/transport.cc",
@@ -30,7 +32,7 @@ SOURCES = [
 HEADERS = ["csrc/compress.h", "csrc/check.h", "csrc/config.h",
            "csrc/registry.h", "csrc/plan.h", "csrc/phase_timer.h",
            "csrc/engine.h", "csrc/backend.h", "csrc/transport.h",
-           "csrc/reducer.h"]
+           "csrc/reducer.h", "csrc/bn_plan.h"]
 EXT_OUT = os.path.join(
     "torch_cgx_amd", "_C" + sysconfig.get_config_var("EXT_SUFFIX"))
 

@@ -11,6 +11,8 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
+from ..ops.fused_bn import bn_act
+
 
 class Bottleneck(nn.Module):
     expansion = 4
@@ -31,12 +33,15 @@ class Bottleneck(nn.Module):
 
     def forward(self, x):
         identity = x
-        out = self.relu(self.bn1(self.conv1(x)))
-        out = self.relu(self.bn2(self.conv2(out)))
-        out = self.bn3(self.conv3(out))
+        out = bn_act(self.bn1, self.conv1(x))
+        out = bn_act(self.bn2, self.conv2(out))
+        out = self.conv3(out)
         if self.downsample is not None:
+            # stock on purpose: its output feeds the next block undamped, and
+            # the native kernels' 0.25 ms were not worth the larger drift
+            # from the stock results (benchmarks/RESULTS.md)
             identity = self.downsample(x)
-        return self.relu(out + identity)
+        return bn_act(self.bn3, out, identity)
 
 
 class ResNet(nn.Module):
@@ -76,7 +81,7 @@ class ResNet(nn.Module):
         return nn.Sequential(*layers)
 
     def forward(self, x):
-        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        x = self.maxpool(bn_act(self.bn1, self.conv1(x)))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         x = self.avgpool(x).flatten(1)
         return self.fc(x)
