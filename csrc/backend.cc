@@ -1,5 +1,6 @@
 // Implementation of ProcessGroupCGX (see backend.h).
 #include "backend.h"
+#include "collectives.h"
 
 #include <ATen/hip/impl/HIPCachingAllocatorMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
@@ -380,21 +381,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::allgather(
   auto outs = outputs[0];
   return collective(outs, in.device(), c10d::OpType::ALLGATHER,
                     [this, in, outs](hipStream_t s) {
-                      CGX_NCCL_CHECK(ncclGroupStart());
-                      for (int p = 0; p < size_; p++) {
-                        if (p == rank_) continue;
-                        CGX_NCCL_CHECK(ncclSend(in.data_ptr(), in.numel(),
-                                                nccl_dtype(in), p, comm_, s));
-                        CGX_NCCL_CHECK(ncclRecv(outs[p].data_ptr(),
-                                                outs[p].numel(),
-                                                nccl_dtype(outs[p]), p, comm_,
-                                                s));
-                      }
-                      CGX_NCCL_CHECK(ncclGroupEnd());
-                      CGX_HIP_CHECK(hipMemcpyAsync(
-                          outs[rank_].data_ptr(), in.data_ptr(),
-                          in.numel() * in.element_size(),
-                          hipMemcpyDeviceToDevice, s));
+                      coll::allgather(tr_.get(), rank_, size_, in, outs, s);
                     });
 }
 
@@ -427,25 +414,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::gather(
       rank_ == root ? outputs[0] : std::vector<at::Tensor>{};
   return collective(outs.empty() ? inputs : outs, in.device(),
                     c10d::OpType::GATHER, [this, in, outs, root](hipStream_t s) {
-                      if (rank_ == root) {
-                        CGX_NCCL_CHECK(ncclGroupStart());
-                        for (int p = 0; p < size_; p++) {
-                          if (p == root) continue;
-                          CGX_NCCL_CHECK(ncclRecv(outs[p].data_ptr(),
-                                                  outs[p].numel(),
-                                                  nccl_dtype(outs[p]), p,
-                                                  comm_, s));
-                        }
-                        CGX_NCCL_CHECK(ncclGroupEnd());
-                        CGX_HIP_CHECK(hipMemcpyAsync(
-                            outs[root].data_ptr(), in.data_ptr(),
-                            in.numel() * in.element_size(),
-                            hipMemcpyDeviceToDevice, s));
-                      } else {
-                        CGX_NCCL_CHECK(ncclSend(in.data_ptr(), in.numel(),
-                                                nccl_dtype(in), root, comm_,
-                                                s));
-                      }
+                      coll::gather(tr_.get(), rank_, size_, root, in, outs, s);
                     });
 }
 
@@ -463,25 +432,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::scatter(
       rank_ == root ? inputs[0] : std::vector<at::Tensor>{};
   return collective(outputs, out.device(), c10d::OpType::SCATTER,
                     [this, out, ins, root](hipStream_t s) {
-                      if (rank_ == root) {
-                        CGX_NCCL_CHECK(ncclGroupStart());
-                        for (int p = 0; p < size_; p++) {
-                          if (p == root) continue;
-                          CGX_NCCL_CHECK(ncclSend(ins[p].data_ptr(),
-                                                  ins[p].numel(),
-                                                  nccl_dtype(ins[p]), p,
-                                                  comm_, s));
-                        }
-                        CGX_NCCL_CHECK(ncclGroupEnd());
-                        CGX_HIP_CHECK(hipMemcpyAsync(
-                            out.data_ptr(), ins[root].data_ptr(),
-                            out.numel() * out.element_size(),
-                            hipMemcpyDeviceToDevice, s));
-                      } else {
-                        CGX_NCCL_CHECK(ncclRecv(out.data_ptr(), out.numel(),
-                                                nccl_dtype(out), root, comm_,
-                                                s));
-                      }
+                      coll::scatter(tr_.get(), rank_, size_, root, ins, out, s);
                     });
 }
 
@@ -541,43 +492,11 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::alltoall_base(
     c10d::AllToAllOptions o;
     return cpu_delegate().alltoall_base(output, input, os, is, o);
   }
-  at::Tensor in = input, out = output;
-  std::vector<int64_t> osplit = outputSplitSizes, isplit = inputSplitSizes;
-  if (osplit.empty()) {
-    TORCH_CHECK(out.numel() % size_ == 0 && in.numel() % size_ == 0,
-                "cgx: alltoall_base tensor not divisible by world size");
-    osplit.assign(size_, out.numel() / size_);
-    isplit.assign(size_, in.numel() / size_);
-  } else {
-    // splits are in units of dim-0 rows
-    int64_t orow = out.dim() > 0 && out.size(0) > 0 ? out.numel() / out.size(0) : 1;
-    int64_t irow = in.dim() > 0 && in.size(0) > 0 ? in.numel() / in.size(0) : 1;
-    for (auto& v : osplit) v *= orow;
-    for (auto& v : isplit) v *= irow;
-  }
   return collective({output}, input.device(), c10d::OpType::ALLTOALL_BASE,
-                    [this, in, out, osplit, isplit](hipStream_t s) {
-                      const int es = in.element_size();
-                      std::vector<int64_t> ooff(size_, 0), ioff(size_, 0);
-                      for (int p = 1; p < size_; p++) {
-                        ooff[p] = ooff[p - 1] + osplit[p - 1];
-                        ioff[p] = ioff[p - 1] + isplit[p - 1];
-                      }
-                      CGX_NCCL_CHECK(ncclGroupStart());
-                      for (int p = 0; p < size_; p++) {
-                        if (p == rank_) continue;
-                        CGX_NCCL_CHECK(ncclSend(
-                            static_cast<char*>(in.data_ptr()) + ioff[p] * es,
-                            isplit[p], nccl_dtype(in), p, comm_, s));
-                        CGX_NCCL_CHECK(ncclRecv(
-                            static_cast<char*>(out.data_ptr()) + ooff[p] * es,
-                            osplit[p], nccl_dtype(out), p, comm_, s));
-                      }
-                      CGX_NCCL_CHECK(ncclGroupEnd());
-                      CGX_HIP_CHECK(hipMemcpyAsync(
-                          static_cast<char*>(out.data_ptr()) + ooff[rank_] * es,
-                          static_cast<char*>(in.data_ptr()) + ioff[rank_] * es,
-                          isplit[rank_] * es, hipMemcpyDeviceToDevice, s));
+                    [&](hipStream_t s) {  // runs before collective returns
+                      coll::alltoall_base(tr_.get(), rank_, size_, input,
+                                          output, inputSplitSizes,
+                                          outputSplitSizes, s);
                     });
 }
 
@@ -609,23 +528,7 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::alltoall(
   std::vector<at::Tensor> ins = inputs, outs = outputs;
   return collective(outputs, inputs[0].device(), c10d::OpType::ALLTOALL,
                     [this, ins, outs](hipStream_t s) {
-                      CGX_NCCL_CHECK(ncclGroupStart());
-                      for (int p = 0; p < size_; p++) {
-                        if (p == rank_) continue;
-                        CGX_NCCL_CHECK(ncclSend(ins[p].data_ptr(),
-                                                ins[p].numel(),
-                                                nccl_dtype(ins[p]), p, comm_,
-                                                s));
-                        CGX_NCCL_CHECK(ncclRecv(outs[p].data_ptr(),
-                                                outs[p].numel(),
-                                                nccl_dtype(outs[p]), p, comm_,
-                                                s));
-                      }
-                      CGX_NCCL_CHECK(ncclGroupEnd());
-                      CGX_HIP_CHECK(hipMemcpyAsync(
-                          outs[rank_].data_ptr(), ins[rank_].data_ptr(),
-                          ins[rank_].numel() * ins[rank_].element_size(),
-                          hipMemcpyDeviceToDevice, s));
+                      coll::alltoall(tr_.get(), rank_, size_, ins, outs, s);
                     });
 }
 
@@ -660,9 +563,8 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::send(
   }
   return collective(tensors, t.device(), c10d::OpType::SEND,
                     [this, t, dstRank](hipStream_t s) {
-                      CGX_NCCL_CHECK(ncclSend(t.data_ptr(), t.numel(),
-                                              nccl_dtype(t), dstRank, comm_,
-                                              s));
+                      const coll::Buf b = coll::buf_of(t);
+                      tr_->exchange({{b.ptr, b.bytes, dstRank}}, {}, s);
                     });
 }
 
@@ -681,9 +583,8 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::recv(
   }
   return collective(tensors, t.device(), c10d::OpType::RECV,
                     [this, t, srcRank](hipStream_t s) {
-                      CGX_NCCL_CHECK(ncclRecv(t.data_ptr(), t.numel(),
-                                              nccl_dtype(t), srcRank, comm_,
-                                              s));
+                      const coll::Buf b = coll::buf_of(t);
+                      tr_->exchange({}, {{b.ptr, b.bytes, srcRank}}, s);
                     });
 }
 
@@ -711,9 +612,8 @@ c10::intrusive_ptr<c10d::Work> ProcessGroupCGX::recvAnysource(
               "cgx: bad announced source rank ", src);
   return collective(tensors, t.device(), c10d::OpType::RECVANYSOURCE,
                     [this, t, src](hipStream_t s) {
-                      CGX_NCCL_CHECK(ncclRecv(t.data_ptr(), t.numel(),
-                                              nccl_dtype(t), src, comm_,
-                                              s));
+                      const coll::Buf b = coll::buf_of(t);
+                      tr_->exchange({}, {{b.ptr, b.bytes, src}}, s);
                     });
 }
 

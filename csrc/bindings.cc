@@ -20,6 +20,7 @@
 
 #include "backend.h"
 #include "bn_plan.h"
+#include "collectives.h"
 #include "reducer.h"
 
 namespace cgx {
@@ -200,6 +201,90 @@ void py_loopback_hierarchical(std::vector<at::Tensor> buckets,
                [&](Reducer& red, hipStream_t qs, int r) {
                  return red.allreduce(buckets[r], qs, &reg.info, reg.matched);
                });
+}
+
+// The backend's p2p collectives (collectives.h) with real peers on one GPU:
+// rank r runs the function ProcessGroupCGX runs, over a loopback transport,
+// on inputs[r] / outputs[r], the tensor lists its backend method would get
+// (alltoall_base: one tensor each; the non-root side of gather/scatter: none).
+void py_loopback_collective(
+    const std::string& name, std::vector<std::vector<at::Tensor>> inputs,
+    std::vector<std::vector<at::Tensor>> outputs, int64_t root,
+    std::vector<std::vector<int64_t>> in_splits,
+    std::vector<std::vector<int64_t>> out_splits) {
+  const int ws = (int)inputs.size();
+  TORCH_CHECK(ws >= 1 && (int)outputs.size() == ws && root >= 0 && root < ws,
+              "loopback_collective: one input and one output list per rank "
+              "and a root among them");
+  TORCH_CHECK((in_splits.empty() || (int)in_splits.size() == ws) &&
+                  (out_splits.empty() || (int)out_splits.size() == ws),
+              "loopback_collective: splits are per rank, or empty");
+  in_splits.resize(ws);
+  out_splits.resize(ws);
+  // per name: the list lengths of rank r, and the call it makes
+  std::function<size_t(int)> n_in, n_out;
+  std::function<void(Transport*, int, hipStream_t)> call;
+  const auto one = [](int) { return (size_t)1; };
+  const auto all = [ws](int) { return (size_t)ws; };
+  const auto at_root = [ws, root](int r) { return r == root ? (size_t)ws : 0; };
+  if (name == "allgather") {
+    n_in = one; n_out = all;
+    call = [&](Transport* tr, int r, hipStream_t s) {
+      coll::allgather(tr, r, ws, inputs[r][0], outputs[r], s);
+    };
+  } else if (name == "gather") {
+    n_in = one; n_out = at_root;
+    call = [&](Transport* tr, int r, hipStream_t s) {
+      coll::gather(tr, r, ws, (int)root, inputs[r][0], outputs[r], s);
+    };
+  } else if (name == "scatter") {
+    n_in = at_root; n_out = one;
+    call = [&](Transport* tr, int r, hipStream_t s) {
+      coll::scatter(tr, r, ws, (int)root, inputs[r], outputs[r][0], s);
+    };
+  } else if (name == "alltoall") {
+    n_in = all; n_out = all;
+    call = [&](Transport* tr, int r, hipStream_t s) {
+      coll::alltoall(tr, r, ws, inputs[r], outputs[r], s);
+    };
+  } else if (name == "alltoall_base") {
+    n_in = one; n_out = one;
+    call = [&](Transport* tr, int r, hipStream_t s) {
+      coll::alltoall_base(tr, r, ws, inputs[r][0], outputs[r][0], in_splits[r],
+                          out_splits[r], s);
+    };
+  } else {
+    TORCH_CHECK(false, "loopback_collective: unknown collective '", name, "'");
+  }
+  c10::optional<at::Device> device;
+  for (int r = 0; r < ws; r++) {
+    TORCH_CHECK(inputs[r].size() == n_in(r) && outputs[r].size() == n_out(r),
+                "loopback_collective: rank ", r, " of ", name, " takes ",
+                n_in(r), " input and ", n_out(r), " output tensors");
+    for (const auto* ts : {&inputs[r], &outputs[r]})
+      for (const at::Tensor& t : *ts) {
+        TORCH_CHECK(t.is_cuda() && t.is_contiguous(),
+                    "loopback_collective: CUDA contiguous tensors required");
+        if (!device) device = t.device();
+        TORCH_CHECK(t.device() == *device,
+                    "loopback_collective: tensors must share one device");
+      }
+  }
+  const int dev = device->index();
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  // the rank streams do not order behind the caller's: drain its work first
+  CGX_HIP_CHECK(hipStreamSynchronize(
+      c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev).stream()));
+  LoopbackHub hub(ws);
+  std::vector<LoopbackTransport> trs;
+  for (int r = 0; r < ws; r++) trs.emplace_back(&hub, r);
+  run_rank_threads(
+      ws, dev,
+      [&](int r, hipStream_t s) {
+        call(&trs[r], r, s);
+        CGX_HIP_CHECK(hipStreamSynchronize(s));
+      },
+      [&] { hub.abort(); });
 }
 
 // Copy a routed group's descs (followed by cum, if any) to the device.
@@ -704,6 +789,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "n_nodes*local_size ranks on one GPU via loopback transports: intra "
         "allreduce -> leader cross reduction -> intra broadcast, or the "
         "flat path under CGX_INTRA_BROADCAST=0.");
+  m.def("loopback_collective", &cgx::py_loopback_collective, py::arg("name"),
+        py::arg("inputs"), py::arg("outputs"), py::arg("root") = 0,
+        py::arg("in_splits") = std::vector<std::vector<int64_t>>{},
+        py::arg("out_splits") = std::vector<std::vector<int64_t>>{},
+        "Run one of the backend's p2p collectives (allgather, gather, "
+        "scatter, alltoall, alltoall_base) at world_size=len(inputs) on one "
+        "GPU via the loopback transport; inputs[r] / outputs[r] are rank r's "
+        "tensor lists, in_splits[r] / out_splits[r] its alltoall_base splits.");
   m.def("quantize", &cgx::py_quantize, py::arg("x"), py::arg("bits"),
         py::arg("bucket_size"), py::arg("stochastic") = false,
         py::arg("seed") = 0, py::arg("skip_incomplete") = false,

@@ -26,13 +26,14 @@ SOURCES = [
     "csrc/engine.cc",
     "csrc/transport.cc",
     "csrc/reducer.cc",
+    "csrc/collectives.cc",
     "csrc/backend.cc",
     "csrc/bindings.cc",
 ]
 HEADERS = ["csrc/compress.h", "csrc/check.h", "csrc/config.h",
            "csrc/registry.h", "csrc/plan.h", "csrc/phase_timer.h",
            "csrc/engine.h", "csrc/backend.h", "csrc/transport.h",
-           "csrc/reducer.h", "csrc/bn_plan.h"]
+           "csrc/reducer.h", "csrc/bn_plan.h", "csrc/collectives.h"]
 EXT_OUT = os.path.join(
     "torch_cgx_amd", "_C" + sysconfig.get_config_var("EXT_SUFFIX"))
 
