@@ -632,6 +632,233 @@ py_bn_act_backward(at::Tensor dy, const at::Tensor& x, const at::Tensor& mean,
   return {dx, dgamma, dbeta, didentity};
 }
 
+hipStream_t bn_stream(const at::Tensor& x) {
+  return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x.device().index())
+      .stream();
+}
+
+// dy as the kernels index it: dense channels_last, 16-byte aligned
+at::Tensor bn_dense_dy(at::Tensor dy) {
+  if (!bn_tensor_ok(dy)) dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
+  if (!bn_tensor_ok(dy)) dy = dy.clone(at::MemoryFormat::ChannelsLast);
+  return dy;
+}
+
+// relu(bn3(x3) + bn_d(xd)) -> (out, mean3, invstd3, meand, invstdd,
+// mask | None); both pairs of running statistics updated in place
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
+           c10::optional<at::Tensor>>
+py_bn_act2_forward(const at::Tensor& x3, const at::Tensor& xd,
+                   const at::Tensor& weight3, const at::Tensor& bias3,
+                   at::Tensor running_mean3, at::Tensor running_var3,
+                   double momentum3, double eps3, const at::Tensor& weightd,
+                   const at::Tensor& biasd, at::Tensor running_meand,
+                   at::Tensor running_vard, double momentumd, double epsd,
+                   bool relu) {
+  TORCH_CHECK(py_bn_eligible(x3), "bn_act2_forward: input is not eligible");
+  TORCH_CHECK(bn_tensor_ok(xd) && xd.sizes() == x3.sizes() &&
+                  xd.device() == x3.device(),
+              "bn_act2_forward: both inputs must have the same shape");
+  const BnPlan p = bn_plan_of(x3);
+  const int64_t c = p.channels;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x3.device().index());
+  auto out = at::empty(x3.sizes(), x3.options(), at::MemoryFormat::ChannelsLast);
+  auto stats = x3.options().dtype(at::kFloat);
+  auto mean3 = at::empty({c}, stats), invstd3 = at::empty({c}, stats);
+  auto meand = at::empty({c}, stats), invstdd = at::empty({c}, stats);
+  c10::optional<at::Tensor> mask;
+  if (relu) mask = at::empty({x3.numel() / 8}, x3.options().dtype(at::kByte));
+  auto part = at::empty({2 * (2 * p.partial_floats + p.grid)}, stats);
+  BnJoinArgs j{};
+  j.a.x = x3.data_ptr();
+  j.a.weight = bn_channel_vec(weight3, c, "weight");
+  j.a.bias = bn_channel_vec(bias3, c, "bias");
+  j.a.running_mean = bn_channel_vec(running_mean3, c, "running_mean");
+  j.a.running_var = bn_channel_vec(running_var3, c, "running_var");
+  j.a.momentum = (float)momentum3;
+  j.a.eps = (float)eps3;
+  j.a.mean = mean3.data_ptr<float>();
+  j.a.invstd = invstd3.data_ptr<float>();
+  j.b.x = xd.data_ptr();
+  j.b.weight = bn_channel_vec(weightd, c, "identity weight");
+  j.b.bias = bn_channel_vec(biasd, c, "identity bias");
+  j.b.running_mean = bn_channel_vec(running_meand, c, "identity running_mean");
+  j.b.running_var = bn_channel_vec(running_vard, c, "identity running_var");
+  j.b.momentum = (float)momentumd;
+  j.b.eps = (float)epsd;
+  j.b.mean = meand.data_ptr<float>();
+  j.b.invstd = invstdd.data_ptr<float>();
+  j.relu = relu;
+  j.out = out.data_ptr();
+  j.mask = relu ? mask->data_ptr<uint8_t>() : nullptr;
+  j.part = part.data_ptr<float>();
+  launch_bn_join_forward(p, j, bn_stream(x3));
+  return {out, mean3, invstd3, meand, invstdd, mask};
+}
+
+// -> (dx3, dxd, dgamma3, dbeta3, dgammad, dbetad)
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
+           at::Tensor>
+py_bn_act2_backward(at::Tensor dy, const at::Tensor& x3, const at::Tensor& xd,
+                    const at::Tensor& mean3, const at::Tensor& invstd3,
+                    const at::Tensor& weight3, const at::Tensor& meand,
+                    const at::Tensor& invstdd, const at::Tensor& weightd,
+                    const c10::optional<at::Tensor>& mask) {
+  TORCH_CHECK(py_bn_eligible(x3), "bn_act2_backward: input is not eligible");
+  TORCH_CHECK(bn_tensor_ok(xd) && xd.sizes() == x3.sizes() &&
+                  xd.device() == x3.device(),
+              "bn_act2_backward: both inputs must have the same shape");
+  const BnPlan p = bn_plan_of(x3);
+  const int64_t c = p.channels;
+  TORCH_CHECK(dy.is_cuda() && dy.device() == x3.device() &&
+                  dy.scalar_type() == at::kBFloat16 && dy.sizes() == x3.sizes(),
+              "bn_act2_backward: dy must match the input");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x3.device().index());
+  dy = bn_dense_dy(dy);
+  if (mask.has_value())
+    TORCH_CHECK(mask->is_cuda() && mask->scalar_type() == at::kByte &&
+                    mask->is_contiguous() && mask->numel() == x3.numel() / 8,
+                "bn_act2_backward: mask must hold one bit per element");
+  auto dx3 = at::empty(x3.sizes(), x3.options(), at::MemoryFormat::ChannelsLast);
+  auto dxd = at::empty(x3.sizes(), x3.options(), at::MemoryFormat::ChannelsLast);
+  auto stats = x3.options().dtype(at::kFloat);
+  auto dgamma3 = at::empty({c}, stats), dbeta3 = at::empty({c}, stats);
+  auto dgammad = at::empty({c}, stats), dbetad = at::empty({c}, stats);
+  auto part = at::empty({3 * p.partial_floats}, stats);
+  BnJoinArgs j{};
+  j.a.x = x3.data_ptr();
+  j.a.mean = bn_channel_vec(mean3, c, "mean");
+  j.a.invstd = bn_channel_vec(invstd3, c, "invstd");
+  j.a.weight = bn_channel_vec(weight3, c, "weight");
+  j.a.dx = dx3.data_ptr();
+  j.a.dgamma = dgamma3.data_ptr<float>();
+  j.a.dbeta = dbeta3.data_ptr<float>();
+  j.b.x = xd.data_ptr();
+  j.b.mean = bn_channel_vec(meand, c, "identity mean");
+  j.b.invstd = bn_channel_vec(invstdd, c, "identity invstd");
+  j.b.weight = bn_channel_vec(weightd, c, "identity weight");
+  j.b.dx = dxd.data_ptr();
+  j.b.dgamma = dgammad.data_ptr<float>();
+  j.b.dbeta = dbetad.data_ptr<float>();
+  j.dy = dy.data_ptr();
+  j.mask = mask.has_value() ? mask->data_ptr<uint8_t>() : nullptr;
+  j.part = part.data_ptr<float>();
+  launch_bn_join_backward(p, j, bn_stream(x3));
+  return {dx3, dxd, dgamma3, dbeta3, dgammad, dbetad};
+}
+
+BnPoolPlan bn_pool_plan_of(const at::Tensor& x) {
+  return bn_pool_plan(x.size(0), x.size(2), x.size(3), x.size(1));
+}
+
+// maxpool3x3/2/1(relu(bn(x))) -> (pooled, mean, invstd, arg); arg holds one
+// byte per pooled element: the window position of its maximum
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
+py_bn_act_pool_forward(const at::Tensor& x, const at::Tensor& weight,
+                       const at::Tensor& bias, at::Tensor running_mean,
+                       at::Tensor running_var, double momentum, double eps) {
+  TORCH_CHECK(py_bn_eligible(x), "bn_act_pool_forward: input is not eligible");
+  const BnPlan p = bn_plan_of(x);
+  const BnPoolPlan g = bn_pool_plan_of(x);
+  const int64_t c = p.channels;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device().index());
+  auto out = at::empty({x.size(0), c, g.oh, g.ow}, x.options(),
+                       at::MemoryFormat::ChannelsLast);
+  auto arg = at::empty({x.size(0), c, g.oh, g.ow},
+                       x.options().dtype(at::kByte),
+                       at::MemoryFormat::ChannelsLast);
+  auto stats = x.options().dtype(at::kFloat);
+  auto mean = at::empty({c}, stats), invstd = at::empty({c}, stats);
+  auto part = bn_workspace(p, x);
+  BnPoolArgs a{};
+  a.x = x.data_ptr();
+  a.weight = bn_channel_vec(weight, c, "weight");
+  a.bias = bn_channel_vec(bias, c, "bias");
+  a.running_mean = bn_channel_vec(running_mean, c, "running_mean");
+  a.running_var = bn_channel_vec(running_var, c, "running_var");
+  a.momentum = (float)momentum;
+  a.eps = (float)eps;
+  a.mean = mean.data_ptr<float>();
+  a.invstd = invstd.data_ptr<float>();
+  a.out = out.data_ptr();
+  a.arg = arg.data_ptr<uint8_t>();
+  a.part = part.data_ptr<float>();
+  launch_bn_pool_forward(p, g, a, bn_stream(x));
+  return {out, mean, invstd, arg};
+}
+
+// -> (dx, dgamma, dbeta)
+std::tuple<at::Tensor, at::Tensor, at::Tensor>
+py_bn_act_pool_backward(at::Tensor dy, const at::Tensor& x,
+                        const at::Tensor& mean, const at::Tensor& invstd,
+                        const at::Tensor& weight, const at::Tensor& arg) {
+  TORCH_CHECK(py_bn_eligible(x), "bn_act_pool_backward: input is not eligible");
+  const BnPlan p = bn_plan_of(x);
+  const BnPoolPlan g = bn_pool_plan_of(x);
+  const int64_t c = p.channels;
+  const std::vector<int64_t> pooled = {x.size(0), c, g.oh, g.ow};
+  TORCH_CHECK(dy.is_cuda() && dy.device() == x.device() &&
+                  dy.scalar_type() == at::kBFloat16 && dy.sizes() == at::IntArrayRef(pooled),
+              "bn_act_pool_backward: dy must have the pooled shape");
+  TORCH_CHECK(arg.is_cuda() && arg.device() == x.device() &&
+                  arg.scalar_type() == at::kByte && arg.sizes() == at::IntArrayRef(pooled) &&
+                  arg.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                  reinterpret_cast<uintptr_t>(arg.data_ptr()) % 8 == 0,
+              "bn_act_pool_backward: arg must be the forward's");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device().index());
+  dy = bn_dense_dy(dy);
+  auto dx = at::empty(x.sizes(), x.options(), at::MemoryFormat::ChannelsLast);
+  auto stats = x.options().dtype(at::kFloat);
+  auto dgamma = at::empty({c}, stats), dbeta = at::empty({c}, stats);
+  auto part = bn_workspace(p, x);
+  BnPoolArgs a{};
+  a.x = x.data_ptr();
+  a.mean = bn_channel_vec(mean, c, "mean");
+  a.invstd = bn_channel_vec(invstd, c, "invstd");
+  a.weight = bn_channel_vec(weight, c, "weight");
+  a.arg = arg.data_ptr<uint8_t>();
+  a.dy = dy.data_ptr();
+  a.dx = dx.data_ptr();
+  a.dgamma = dgamma.data_ptr<float>();
+  a.dbeta = dbeta.data_ptr<float>();
+  a.part = part.data_ptr<float>();
+  launch_bn_pool_backward(p, g, a, bn_stream(x));
+  return {dx, dgamma, dbeta};
+}
+
+// Test seam: the pooling geometry the stem kernels use, for one h x w image.
+// -> (windows [oh*ow, 9], covers [h*w, 4, 2]): row o of `windows` holds the
+// input pixel (ih*w + iw) each window position of pooled pixel o reads, -1
+// for padding; row i of `covers` holds the (pooled pixel, window position)
+// pairs the backward visits for input pixel i, in that order, -1 beyond them.
+std::tuple<at::Tensor, at::Tensor> py_bn_pool_geometry(int64_t h, int64_t w) {
+  TORCH_CHECK(h >= 1 && w >= 1 && h * w <= kBnMaxRows, "bn_pool_geometry: bad");
+  const BnPoolPlan g = bn_pool_plan(1, h, w, 8);
+  auto opt = at::TensorOptions().dtype(at::kLong);
+  auto windows = at::full({(int64_t)g.oh * g.ow, 9}, -1, opt);
+  auto covers = at::full({h * w, 4, 2}, -1, opt);
+  int64_t* wi = windows.data_ptr<int64_t>();
+  int64_t* co = covers.data_ptr<int64_t>();
+  for (int oh = 0; oh < g.oh; oh++)
+    for (int ow = 0; ow < g.ow; ow++)
+      for (int k = 0; k < 9; k++) {
+        const int ih = pool_in(oh, k / 3), iw = pool_in(ow, k % 3);
+        if (ih >= 0 && ih < g.h && iw >= 0 && iw < g.w)
+          wi[((int64_t)oh * g.ow + ow) * 9 + k] = (int64_t)ih * g.w + iw;
+      }
+  for (int ih = 0; ih < g.h; ih++)
+    for (int iw = 0; iw < g.w; iw++) {
+      int n = 0;
+      for (int oh = pool_cover_lo(ih); oh <= pool_cover_hi(ih, g.oh); oh++)
+        for (int ow = pool_cover_lo(iw); ow <= pool_cover_hi(iw, g.ow); ow++) {
+          int64_t* e = co + (((int64_t)ih * g.w + iw) * 4 + n++) * 2;
+          e[0] = (int64_t)oh * g.ow + ow;
+          e[1] = pool_k(ih, oh) * 3 + pool_k(iw, ow);
+        }
+    }
+  return {windows, covers};
+}
+
 py::dict py_bn_plan(int64_t rows, int64_t channels) {
   const BnPlan p = bn_plan(rows, channels);
   py::dict d;
@@ -853,6 +1080,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("mean"), py::arg("invstd"), py::arg("weight"),
         py::arg("mask"), py::arg("has_identity"),
         "Backward of bn_act_forward -> (dx, dgamma, dbeta, didentity | None).");
+  m.def("bn_act2_forward", &cgx::py_bn_act2_forward,
+        "relu(bn3(x3) + bn_d(xd)) with both BatchNorms in training mode: "
+        "(x3, xd, weight3, bias3, running_mean3, running_var3, momentum3, "
+        "eps3, weightd, biasd, running_meand, running_vard, momentumd, epsd, "
+        "relu) -> (out, mean3, invstd3, meand, invstdd, mask | None).");
+  m.def("bn_act2_backward", &cgx::py_bn_act2_backward,
+        "Backward of bn_act2_forward: (dy, x3, xd, mean3, invstd3, weight3, "
+        "meand, invstdd, weightd, mask) -> (dx3, dxd, dgamma3, dbeta3, "
+        "dgammad, dbetad).");
+  m.def("bn_act_pool_forward", &cgx::py_bn_act_pool_forward, py::arg("x"),
+        py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
+        py::arg("running_var"), py::arg("momentum"), py::arg("eps"),
+        "max_pool2d(relu(bn(x)), 3, 2, 1) in training mode -> (pooled, mean, "
+        "invstd, arg); arg is one byte per pooled element.");
+  m.def("bn_act_pool_backward", &cgx::py_bn_act_pool_backward, py::arg("dy"),
+        py::arg("x"), py::arg("mean"), py::arg("invstd"), py::arg("weight"),
+        py::arg("arg"),
+        "Backward of bn_act_pool_forward -> (dx, dgamma, dbeta).");
+  m.def("bn_pool_geometry", &cgx::py_bn_pool_geometry, py::arg("h"),
+        py::arg("w"),
+        "Test seam: (windows [oh*ow, 9], covers [h*w, 4, 2]) of the stem's "
+        "3x3/2/1 pooling as the kernels index it.");
   m.def("bn_eligible", &cgx::py_bn_eligible, py::arg("x"),
         "True where the fused BatchNorm kernels take `x`: CUDA, bf16, dense "
         "channels_last, and a shape bn_plan calls eligible.");

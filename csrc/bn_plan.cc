@@ -32,4 +32,17 @@ BnPlan bn_plan(int64_t rows, int64_t channels) {
   return p;
 }
 
+BnPoolPlan bn_pool_plan(int64_t n, int64_t h, int64_t w, int64_t channels) {
+  BnPoolPlan g;
+  g.n = (int)n;
+  g.h = (int)h;
+  g.w = (int)w;
+  g.oh = pool_out(g.h);
+  g.ow = pool_out(g.w);
+  g.cgs = (int)(channels / 8);
+  g.threads = (int64_t)g.n * g.oh * g.ow * g.cgs;
+  g.grid = (int)((g.threads + kBnThreads - 1) / kBnThreads);
+  return g;
+}
+
 }  // namespace cgx

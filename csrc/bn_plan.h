@@ -110,4 +110,86 @@ struct BnBackwardArgs {
 void launch_bn_backward(const BnPlan& p, const BnBackwardArgs& a,
                         hipStream_t stream);
 
+// ---- residual join of two BatchNorms: relu(bn3(x3) + bn_d(xd)) -------------
+//
+// Same plan for both operands (same shape).  `part` holds two forward
+// workspaces back to back (2 * (2*partial_floats + grid) floats); the backward
+// uses its first 3*partial_floats.
+struct BnOperand {
+  const void* x;  // [R, C] bf16
+  const float* weight;
+  const float* bias;    // forward only
+  float* running_mean;  // forward only
+  float* running_var;   // forward only
+  float momentum, eps;  // forward only
+  float* mean;          // [C], written by the forward, read by the backward
+  float* invstd;        // [C]
+  void* dx;             // [R, C] bf16, backward only
+  float* dgamma;        // [C], backward only
+  float* dbeta;         // [C], backward only
+};
+struct BnJoinArgs {
+  BnOperand a, b;  // the block's bn3 and its downsample BatchNorm
+  bool relu;
+  void* out;        // forward: [R, C] bf16
+  const void* dy;   // backward: [R, C] bf16
+  uint8_t* mask;    // [R*C/8]; written by the forward, read by the backward
+  float* part;
+};
+void launch_bn_join_forward(const BnPlan& p, const BnJoinArgs& a,
+                            hipStream_t stream);
+void launch_bn_join_backward(const BnPlan& p, const BnJoinArgs& a,
+                             hipStream_t stream);
+
+// ---- stem: BatchNorm + ReLU + 3x3 / stride 2 / pad 1 max-pool ---------------
+//
+// Along one axis of `in` pixels there are (in-1)/2 + 1 pooled positions;
+// pooled position o looks at the input coordinates 2*o-1+k, k = 0..2, of
+// which those in [0, in) exist.  Input coordinate i is covered by the pooled
+// positions i/2 .. min((i+1)/2, out-1): one if i is even, two if it is odd
+// and not cut off by the border.  A window position is kh*3+kw; kPoolNone
+// marks a pooled element that passes no gradient (its value is <= 0).
+constexpr int kPoolNone = 9;
+
+struct BnPoolPlan {
+  int n = 0, h = 0, w = 0;  // input pixels
+  int oh = 0, ow = 0;       // pooled pixels
+  int cgs = 0;              // channel groups per pixel
+  int64_t threads = 0;      // forward: one per (pooled pixel, channel group)
+  int grid = 0;             // forward workgroups of kBnThreads
+};
+BnPoolPlan bn_pool_plan(int64_t n, int64_t h, int64_t w, int64_t channels);
+
+__host__ __device__ inline int pool_out(int in) { return (in - 1) / 2 + 1; }
+__host__ __device__ inline int pool_in(int o, int k) { return 2 * o - 1 + k; }
+__host__ __device__ inline int pool_cover_lo(int i) { return i / 2; }
+__host__ __device__ inline int pool_cover_hi(int i, int out) {
+  const int hi = (i + 1) / 2;
+  return hi < out ? hi : out - 1;
+}
+// window position (along one axis) at which pooled position o sees input i
+__host__ __device__ inline int pool_k(int i, int o) { return i - (2 * o - 1); }
+
+struct BnPoolArgs {
+  const void* x;  // [N, H, W, C] bf16
+  const float* weight;
+  const float* bias;
+  float* running_mean;
+  float* running_var;
+  float momentum, eps;
+  float* mean;
+  float* invstd;
+  void* out;        // forward: [N, OH, OW, C] bf16
+  uint8_t* arg;     // [N, OH, OW, C] window position of the maximum
+  const void* dy;   // backward: [N, OH, OW, C] bf16
+  void* dx;         // backward: [N, H, W, C] bf16
+  float* dgamma;
+  float* dbeta;
+  float* part;      // as for launch_bn_forward
+};
+void launch_bn_pool_forward(const BnPlan& p, const BnPoolPlan& g,
+                            const BnPoolArgs& a, hipStream_t stream);
+void launch_bn_pool_backward(const BnPlan& p, const BnPoolPlan& g,
+                             const BnPoolArgs& a, hipStream_t stream);
+
 }  // namespace cgx

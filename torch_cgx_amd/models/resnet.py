@@ -11,7 +11,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from ..ops.fused_bn import bn_act
+from ..ops.fused_bn import bn_act, bn_act_pool
 
 
 class Bottleneck(nn.Module):
@@ -37,10 +37,11 @@ class Bottleneck(nn.Module):
         out = bn_act(self.bn2, self.conv2(out))
         out = self.conv3(out)
         if self.downsample is not None:
-            # stock on purpose: its output feeds the next block undamped, and
-            # the native kernels' 0.25 ms were not worth the larger drift
-            # from the stock results (benchmarks/RESULTS.md)
-            identity = self.downsample(x)
+            # the downsample BatchNorm is the second operand of bn3's sweeps:
+            # its output and its gradient never go through memory
+            # (benchmarks/RESULTS.md)
+            conv, bn = self.downsample[0], self.downsample[1]
+            return bn_act(self.bn3, out, conv(x), identity_bn=bn)
         return bn_act(self.bn3, out, identity)
 
 
@@ -81,7 +82,7 @@ class ResNet(nn.Module):
         return nn.Sequential(*layers)
 
     def forward(self, x):
-        x = self.maxpool(bn_act(self.bn1, self.conv1(x)))
+        x = bn_act_pool(self.bn1, self.conv1(x), self.maxpool)
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         x = self.avgpool(x).flatten(1)
         return self.fc(x)
