@@ -21,6 +21,7 @@
 #include "backend.h"
 #include "bn_plan.h"
 #include "collectives.h"
+#include "conv1x1_plan.h"
 #include "reducer.h"
 
 namespace cgx {
@@ -538,6 +539,22 @@ float* bn_channel_vec(const at::Tensor& t, int64_t c, const char* what) {
   return t.data_ptr<float>();
 }
 
+// Partials a 1x1 convolution left for the BatchNorm of `x` (conv1x1_stats):
+// [splits, 2*C + ntiles] fp32.
+BnPartials bn_external_partials(const at::Tensor& part, const at::Tensor& x) {
+  const int64_t c = x.size(1);
+  TORCH_CHECK(part.is_cuda() && part.device() == x.device() &&
+                  part.scalar_type() == at::kFloat && part.dim() == 2 &&
+                  part.is_contiguous() && part.size(0) >= 1 &&
+                  part.size(1) > 2 * c,
+              "bn_act: part must be the [splits, 2*C + ntiles] fp32 partials "
+              "of conv1x1_stats");
+  const int64_t ntiles = part.size(1) - 2 * c;
+  TORCH_CHECK(c % (8 * ntiles) == 0, "bn_act: part has a bad count column");
+  return conv1x1_partials(part.data_ptr<float>(), (int)c, (int)part.size(0),
+                          (int)ntiles);
+}
+
 at::Tensor bn_workspace(const BnPlan& p, const at::Tensor& like) {
   return at::empty({2 * p.partial_floats + p.grid},
                    like.options().dtype(at::kFloat));
@@ -548,7 +565,8 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, c10::optional<at::Tensor>>
 py_bn_act_forward(const at::Tensor& x, const c10::optional<at::Tensor>& identity,
                   const at::Tensor& weight, const at::Tensor& bias,
                   at::Tensor running_mean, at::Tensor running_var,
-                  double momentum, double eps, bool relu) {
+                  double momentum, double eps, bool relu,
+                  const c10::optional<at::Tensor>& stats_part) {
   TORCH_CHECK(py_bn_eligible(x), "bn_act_forward: input is not eligible");
   const BnPlan p = bn_plan_of(x);
   const int64_t c = p.channels;
@@ -578,6 +596,11 @@ py_bn_act_forward(const at::Tensor& x, const c10::optional<at::Tensor>& identity
   a.invstd = invstd.data_ptr<float>();
   a.mask = relu ? mask->data_ptr<uint8_t>() : nullptr;
   a.part = part.data_ptr<float>();
+  BnPartials ext;
+  if (stats_part.has_value()) {
+    ext = bn_external_partials(*stats_part, x);
+    a.stats = &ext;
+  }
   launch_bn_forward(
       p, a, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(
                 x.device().index()).stream());
@@ -654,7 +677,8 @@ py_bn_act2_forward(const at::Tensor& x3, const at::Tensor& xd,
                    double momentum3, double eps3, const at::Tensor& weightd,
                    const at::Tensor& biasd, at::Tensor running_meand,
                    at::Tensor running_vard, double momentumd, double epsd,
-                   bool relu) {
+                   bool relu, const c10::optional<at::Tensor>& stats_part3,
+                   const c10::optional<at::Tensor>& stats_partd) {
   TORCH_CHECK(py_bn_eligible(x3), "bn_act2_forward: input is not eligible");
   TORCH_CHECK(bn_tensor_ok(xd) && xd.sizes() == x3.sizes() &&
                   xd.device() == x3.device(),
@@ -692,6 +716,15 @@ py_bn_act2_forward(const at::Tensor& x3, const at::Tensor& xd,
   j.out = out.data_ptr();
   j.mask = relu ? mask->data_ptr<uint8_t>() : nullptr;
   j.part = part.data_ptr<float>();
+  BnPartials ext3, extd;
+  if (stats_part3.has_value()) {
+    ext3 = bn_external_partials(*stats_part3, x3);
+    j.a.stats = &ext3;
+  }
+  if (stats_partd.has_value()) {
+    extd = bn_external_partials(*stats_partd, xd);
+    j.b.stats = &extd;
+  }
   launch_bn_join_forward(p, j, bn_stream(x3));
   return {out, mean3, invstd3, meand, invstdd, mask};
 }
@@ -912,6 +945,94 @@ std::vector<int64_t> py_bn_partial_offsets(int64_t rows, int64_t channels,
   return offs;
 }
 
+// ---- 1x1 convolution with statistics (conv1x1_plan.h) ----------------------
+
+Conv1x1Plan conv1x1_plan_of(const at::Tensor& x, const at::Tensor& weight,
+                            int64_t max_workgroups) {
+  return conv1x1_plan(x.numel() / x.size(1), x.size(1), weight.size(0),
+                      (int)std::min<int64_t>(max_workgroups, 1 << 20));
+}
+
+// What the kernel takes: a bf16 channels_last activation as for the BatchNorm
+// kernels and a dense bf16 [N, K, 1, 1] weight on the same device.
+bool py_conv1x1_eligible(const at::Tensor& x, const at::Tensor& weight) {
+  return bn_tensor_ok(x) && weight.is_cuda() &&
+         weight.device() == x.device() &&
+         weight.scalar_type() == at::kBFloat16 && weight.dim() == 4 &&
+         weight.size(1) == x.size(1) && weight.size(2) == 1 &&
+         weight.size(3) == 1 && weight.is_contiguous() &&
+         reinterpret_cast<uintptr_t>(weight.data_ptr()) % 16 == 0 &&
+         conv1x1_plan_of(x, weight, 0).eligible;
+}
+
+// conv2d(x, weight) for a 1x1 / stride 1 convolution -> (y, part); part holds
+// the BatchNorm partials of y for bn_act_forward / bn_act2_forward
+std::tuple<at::Tensor, at::Tensor> py_conv1x1_stats(const at::Tensor& x,
+                                                    const at::Tensor& weight,
+                                                    int64_t max_workgroups) {
+  TORCH_CHECK(max_workgroups >= 0, "conv1x1_stats: max_workgroups >= 0");
+  TORCH_CHECK(py_conv1x1_eligible(x, weight),
+              "conv1x1_stats: input or weight is not eligible");
+  const Conv1x1Plan p = conv1x1_plan_of(x, weight, max_workgroups);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device().index());
+  auto y = at::empty({x.size(0), p.n, x.size(2), x.size(3)}, x.options(),
+                     at::MemoryFormat::ChannelsLast);
+  auto part = at::empty({p.splits, p.pstride}, x.options().dtype(at::kFloat));
+  launch_conv1x1_stats(p, x.data_ptr(), weight.data_ptr(), y.data_ptr(),
+                       part.data_ptr<float>(), bn_stream(x));
+  return {y, part};
+}
+
+py::dict py_conv1x1_plan(int64_t rows, int64_t k, int64_t n,
+                         int64_t max_workgroups) {
+  const Conv1x1Plan p = conv1x1_plan(rows, k, n, (int)max_workgroups);
+  py::dict d;
+  d["eligible"] = p.eligible;
+  d["native"] = p.native;
+  d["threads"] = kConvThreads;
+  d["tile_rows"] = kConvTileRows;
+  d["mfma_tiles"] = p.nt;
+  d["tile_channels"] = p.bn;
+  d["ntiles"] = p.ntiles;
+  d["k_chunk"] = p.kc;
+  d["k_chunks"] = p.nchunks;
+  d["resident"] = p.resident;
+  d["row_tiles"] = p.row_tiles;
+  d["splits"] = p.splits;
+  d["grid"] = p.grid;
+  d["tiles_per_split"] = p.tiles_per_split;
+  d["run"] = p.run;
+  d["lds_bytes"] = p.lds_bytes;
+  d["partial_stride"] = p.pstride;
+  d["partial_floats"] = p.partial_floats;
+  return d;
+}
+
+// Test seam: replay the kernel's tile walk on the host.  Entry [wg, i] holds
+// (row0, row1, n0, n1) of the i-th tile of workgroup wg: the rows it stores
+// and counts and its channels; -1 once it has run out of tiles.
+at::Tensor py_conv1x1_walk(int64_t rows, int64_t k, int64_t n,
+                           int64_t max_workgroups) {
+  const Conv1x1Plan p = conv1x1_plan(rows, k, n, (int)max_workgroups);
+  TORCH_CHECK(p.eligible, "conv1x1_walk: shape is not eligible");
+  auto out = at::full({p.grid, p.tiles_per_split, 4}, -1,
+                      at::TensorOptions().dtype(at::kLong));
+  int64_t* o = out.data_ptr<int64_t>();
+  for (int wg = 0; wg < p.grid; wg++) {
+    const int split = conv1x1_split(p, wg), nt = conv1x1_ntile(p, wg);
+    for (int i = 0; i < p.tiles_per_split; i++) {
+      const int t = conv1x1_tile(p, split, i);
+      if (t >= p.row_tiles) break;
+      int64_t* e = o + ((int64_t)wg * p.tiles_per_split + i) * 4;
+      e[0] = (int64_t)t * kConvTileRows;
+      e[1] = std::min<int64_t>(e[0] + kConvTileRows, p.rows);
+      e[2] = (int64_t)nt * p.bn;
+      e[3] = e[2] + p.bn;
+    }
+  }
+  return out;
+}
+
 void py_register_layer(int64_t bucket_idx, int64_t layer_idx, int64_t numel,
                        int64_t bits, int64_t bucket_size) {
   Registry::get().register_layer((int)bucket_idx, (int)layer_idx, numel,
@@ -1072,19 +1193,47 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_act_forward", &cgx::py_bn_act_forward, py::arg("x"),
         py::arg("identity"), py::arg("weight"), py::arg("bias"),
         py::arg("running_mean"), py::arg("running_var"), py::arg("momentum"),
-        py::arg("eps"), py::arg("relu"),
+        py::arg("eps"), py::arg("relu"), py::arg("part") = py::none(),
         "Training-mode BatchNorm2d of a channels_last bf16 tensor, fused with "
         "an optional residual add and ReLU -> (out, mean, invstd, mask | "
-        "None); updates the running statistics in place.");
+        "None); updates the running statistics in place.  With `part`, the "
+        "partials conv1x1_stats returned with x, the statistics pass over x "
+        "is skipped.");
   m.def("bn_act_backward", &cgx::py_bn_act_backward, py::arg("dy"),
         py::arg("x"), py::arg("mean"), py::arg("invstd"), py::arg("weight"),
         py::arg("mask"), py::arg("has_identity"),
         "Backward of bn_act_forward -> (dx, dgamma, dbeta, didentity | None).");
-  m.def("bn_act2_forward", &cgx::py_bn_act2_forward,
+  m.def("bn_act2_forward", &cgx::py_bn_act2_forward, py::arg("x3"),
+        py::arg("xd"), py::arg("weight3"), py::arg("bias3"),
+        py::arg("running_mean3"), py::arg("running_var3"),
+        py::arg("momentum3"), py::arg("eps3"), py::arg("weightd"),
+        py::arg("biasd"), py::arg("running_meand"), py::arg("running_vard"),
+        py::arg("momentumd"), py::arg("epsd"), py::arg("relu"),
+        py::arg("part3") = py::none(), py::arg("partd") = py::none(),
         "relu(bn3(x3) + bn_d(xd)) with both BatchNorms in training mode: "
         "(x3, xd, weight3, bias3, running_mean3, running_var3, momentum3, "
         "eps3, weightd, biasd, running_meand, running_vard, momentumd, epsd, "
-        "relu) -> (out, mean3, invstd3, meand, invstdd, mask | None).");
+        "relu, part3=None, partd=None) -> (out, mean3, invstd3, meand, "
+        "invstdd, mask | None); part3 / partd as `part` of bn_act_forward.");
+  m.def("conv1x1_stats", &cgx::py_conv1x1_stats, py::arg("x"),
+        py::arg("weight"), py::arg("max_workgroups") = 0,
+        "conv2d(x, weight) of a 1x1 / stride 1 / no-bias convolution on a "
+        "channels_last bf16 tensor -> (y, part); part holds the per-channel "
+        "(count, mean, M2) partials of y.  max_workgroups > 0 caps the "
+        "persistent grid.");
+  m.def("conv1x1_eligible", &cgx::py_conv1x1_eligible, py::arg("x"),
+        py::arg("weight"),
+        "True where conv1x1_stats takes (x, weight): CUDA, bf16, dense "
+        "channels_last input, [N, K, 1, 1] weight, and a shape conv1x1_plan "
+        "calls eligible.");
+  m.def("conv1x1_plan", &cgx::py_conv1x1_plan, py::arg("rows"), py::arg("k"),
+        py::arg("n"), py::arg("max_workgroups") = 0,
+        "The launch geometry of conv1x1_stats for [rows, k] x [n, k], and "
+        "`native`: whether the model uses it at this shape.");
+  m.def("conv1x1_walk", &cgx::py_conv1x1_walk, py::arg("rows"), py::arg("k"),
+        py::arg("n"), py::arg("max_workgroups") = 0,
+        "Test seam: [grid, tiles_per_split, 4] int64, (row0, row1, n0, n1) "
+        "of every tile each workgroup visits (-1: none).");
   m.def("bn_act2_backward", &cgx::py_bn_act2_backward,
         "Backward of bn_act2_forward: (dy, x3, xd, mean3, invstd3, weight3, "
         "meand, invstdd, weightd, mask) -> (dx3, dxd, dgamma3, dbeta3, "

@@ -33,6 +33,7 @@
 // multiply-adds below are explicit.
 #include <hip/hip_runtime.h>
 
+#include "bn_moments.h"
 #include "bn_plan.h"
 #include "check.h"
 
@@ -52,13 +53,6 @@ __device__ inline void unpack8(const uint4& v, float (&f)[8]) {
   f[7] = __uint_as_float(v.w & 0xffff0000u);
 }
 
-// fp32 -> bf16 bits, round to nearest even; NaN stays a (quiet) NaN
-__device__ inline unsigned bf16_bits(float f) {
-  const unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-
 __device__ inline uint4 pack8(const unsigned (&b)[8]) {
   return make_uint4(b[0] | (b[1] << 16), b[2] | (b[3] << 16),
                     b[4] | (b[5] << 16), b[6] | (b[7] << 16));
@@ -74,41 +68,6 @@ __device__ inline void load_k(float (&dst)[K], const float* src) {
 #pragma unroll
   for (int j = 0; j < K; j++) dst[j] = src[j];
 }
-
-// ---- running (count, mean, M2) over K channels that share one count --------
-
-template <int K>
-struct Moments {
-  float n = 0.f;
-  float mean[K] = {};
-  float m2[K] = {};
-
-  // Welford step; the count, hence 1/n, is shared by the K channels
-  __device__ void push(const float (&x)[K]) {
-    n += 1.f;
-    const float inv = __builtin_amdgcn_rcpf(n);
-#pragma unroll
-    for (int j = 0; j < K; j++) {
-      const float d = x[j] - mean[j];
-      mean[j] = fmaf(d, inv, mean[j]);
-      m2[j] = fmaf(d, x[j] - mean[j], m2[j]);
-    }
-  }
-
-  // Chan et al. merge of another run; either side may be empty
-  __device__ void merge(float nb, const float (&mb)[K], const float (&m2b)[K]) {
-    const float nt = n + nb;
-    const float fb = nt > 0.f ? nb / nt : 0.f;
-    const float w = n * fb;
-#pragma unroll
-    for (int j = 0; j < K; j++) {
-      const float d = mb[j] - mean[j];
-      mean[j] = fmaf(d, fb, mean[j]);
-      m2[j] = (m2[j] + m2b[j]) + (d * d) * w;
-    }
-    n = nt;
-  }
-};
 
 // Tree merge across the threads tid, tid+lo, tid+2*lo, ... of a workgroup (lo
 // a power of two); threads below `lo` end up with the result.
@@ -210,34 +169,33 @@ __global__ __launch_bounds__(kT) void bn_stats(const uint4* __restrict__ x,
 constexpr int kFinLanes = kT / kBnFinChannels;
 
 __global__ __launch_bounds__(kT) void bn_stats_finalize(
-    const float* __restrict__ pmean, const float* __restrict__ pm2,
-    const float* __restrict__ pcnt, float* __restrict__ mean,
-    float* __restrict__ invstd, float* __restrict__ running_mean,
-    float* __restrict__ running_var, float momentum, float eps, BnPlan p) {
+    BnPartials q, float* __restrict__ mean, float* __restrict__ invstd,
+    float* __restrict__ running_mean, float* __restrict__ running_var,
+    float momentum, float eps) {
   __shared__ float sh[3][kT];
   const int tid = threadIdx.x;
   const int c = blockIdx.x * kBnFinChannels + tid % kBnFinChannels;
   const int lane = tid / kBnFinChannels;
   Moments<1> m;
-  if (c < p.channels) {
-    const int ct = (c / 8) / p.tc;
-    for (int s0 = lane; s0 < p.splits; s0 += 4 * kFinLanes) {
+  if (c < q.channels) {
+    const int ct = (c / 8) / q.tc;
+    for (int s0 = lane; s0 < q.splits; s0 += 4 * kFinLanes) {
       float nb[4], mb[4][1], m2b[4][1];
 #pragma unroll
       for (int u = 0; u < 4; u++) {
         const int s = s0 + u * kFinLanes;
-        const bool live = s < p.splits;
-        const int64_t o = (int64_t)s * p.channels + c;
-        nb[u] = live ? pcnt[s * p.ctiles + ct] : 0.f;
-        mb[u][0] = live ? pmean[o] : 0.f;
-        m2b[u][0] = live ? pm2[o] : 0.f;
+        const bool live = s < q.splits;
+        const int64_t o = (int64_t)s * q.pstride + c;
+        nb[u] = live ? q.cnt[(int64_t)s * q.cstride + ct] : 0.f;
+        mb[u][0] = live ? q.mean[o] : 0.f;
+        m2b[u][0] = live ? q.m2[o] : 0.f;
       }
 #pragma unroll
       for (int u = 0; u < 4; u++) m.merge(nb[u], mb[u], m2b[u]);
     }
   }
   wg_merge<1>(m, sh, tid, kBnFinChannels);
-  if (tid < kBnFinChannels && c < p.channels) {
+  if (tid < kBnFinChannels && c < q.channels) {
     const float var = m.m2[0] / m.n;
     mean[c] = m.mean[0];
     invstd[c] = 1.f / sqrtf(var + eps);
@@ -819,19 +777,32 @@ int fin_grid(const BnPlan& p) {
   return (p.channels + kBnFinChannels - 1) / kBnFinChannels;
 }
 
-// bn_stats + bn_stats_finalize of one activation; `part` as in BnForwardArgs
-void launch_bn_stats(const BnPlan& p, const void* x_, float* part, float* mean,
-                     float* invstd, float* running_mean, float* running_var,
-                     float momentum, float eps, hipStream_t stream) {
-  float* pmean = part;
-  float* pm2 = part + p.partial_floats;
-  float* pcnt = part + 2 * p.partial_floats;
-  const uint4* x = static_cast<const uint4*>(x_);
-  hipLaunchKernelGGL(bn_stats, dim3(p.grid), dim3(kT), 0, stream, x, pmean,
-                     pm2, pcnt, p);
+// bn_stats + bn_stats_finalize of one activation; `part` as in BnForwardArgs.
+// With `stats` the partials are someone else's and only the finalize runs.
+void launch_bn_stats(const BnPlan& p, const void* x_, float* part,
+                     const BnPartials* stats, float* mean, float* invstd,
+                     float* running_mean, float* running_var, float momentum,
+                     float eps, hipStream_t stream) {
+  BnPartials q;
+  if (stats) {
+    q = *stats;
+  } else {
+    float* pmean = part;
+    float* pm2 = part + p.partial_floats;
+    float* pcnt = part + 2 * p.partial_floats;
+    hipLaunchKernelGGL(bn_stats, dim3(p.grid), dim3(kT), 0, stream,
+                       static_cast<const uint4*>(x_), pmean, pm2, pcnt, p);
+    q.mean = pmean;
+    q.m2 = pm2;
+    q.cnt = pcnt;
+    q.channels = p.channels;
+    q.splits = p.splits;
+    q.tc = p.tc;
+    q.pstride = p.channels;
+    q.cstride = p.ctiles;
+  }
   hipLaunchKernelGGL(bn_stats_finalize, dim3(fin_grid(p)), dim3(kT), 0, stream,
-                     pmean, pm2, pcnt, mean, invstd, running_mean, running_var,
-                     momentum, eps, p);
+                     q, mean, invstd, running_mean, running_var, momentum, eps);
 }
 
 }  // namespace
@@ -842,7 +813,7 @@ void launch_bn_forward(const BnPlan& p, const BnForwardArgs& a,
   const uint4* idn = static_cast<const uint4*>(a.identity);
   uint4* out = static_cast<uint4*>(a.out);
   const dim3 grid(p.grid), block(kT);
-  launch_bn_stats(p, a.x, a.part, a.mean, a.invstd, a.running_mean,
+  launch_bn_stats(p, a.x, a.part, a.stats, a.mean, a.invstd, a.running_mean,
                   a.running_var, a.momentum, a.eps, stream);
 #define CGX_BN_APPLY(RELU, ADD)                                              \
   hipLaunchKernelGGL((bn_apply<RELU, ADD>), grid, block, 0, stream, x, idn,  \
@@ -887,9 +858,9 @@ void launch_bn_join_forward(const BnPlan& p, const BnJoinArgs& j,
                             hipStream_t stream) {
   const BnOperand &a = j.a, &b = j.b;
   float* part_b = j.part + 2 * p.partial_floats + p.grid;
-  launch_bn_stats(p, a.x, j.part, a.mean, a.invstd, a.running_mean,
+  launch_bn_stats(p, a.x, j.part, a.stats, a.mean, a.invstd, a.running_mean,
                   a.running_var, a.momentum, a.eps, stream);
-  launch_bn_stats(p, b.x, part_b, b.mean, b.invstd, b.running_mean,
+  launch_bn_stats(p, b.x, part_b, b.stats, b.mean, b.invstd, b.running_mean,
                   b.running_var, b.momentum, b.eps, stream);
   const uint4* x3 = static_cast<const uint4*>(a.x);
   const uint4* xd = static_cast<const uint4*>(b.x);
@@ -943,7 +914,7 @@ void launch_bn_join_backward(const BnPlan& p, const BnJoinArgs& j,
 
 void launch_bn_pool_forward(const BnPlan& p, const BnPoolPlan& g,
                             const BnPoolArgs& a, hipStream_t stream) {
-  launch_bn_stats(p, a.x, a.part, a.mean, a.invstd, a.running_mean,
+  launch_bn_stats(p, a.x, a.part, nullptr, a.mean, a.invstd, a.running_mean,
                   a.running_var, a.momentum, a.eps, stream);
   hipLaunchKernelGGL(bn_apply_pool, dim3(g.grid), dim3(kT), 0, stream,
                      static_cast<const uint4*>(a.x), a.mean, a.invstd, a.weight,

@@ -74,8 +74,25 @@ __host__ __device__ inline int64_t bn_partial_offset(const BnPlan& p, int wg,
   return (int64_t)(wg / p.ctiles) * p.channels + (int64_t)cg * 8;
 }
 
+// Per-channel (count, mean, M2) partials as bn_stats_finalize merges them:
+// partial s of channel c is mean[s*pstride + c], m2[s*pstride + c] with the
+// count cnt[s*cstride + (c/8)/tc].  bn_stats writes [splits, C] arrays and one
+// count per (split, channel tile); the 1x1 convolution (conv1x1_plan.h) writes
+// one [mean | M2 | counts] row per persistent workgroup.
+struct BnPartials {
+  const float* mean = nullptr;
+  const float* m2 = nullptr;
+  const float* cnt = nullptr;
+  int channels = 0;
+  int splits = 0;   // partials per channel
+  int tc = 0;       // channel groups that share one count
+  int pstride = 0;  // floats between consecutive partials of a channel
+  int cstride = 0;  // floats between consecutive counts of a channel tile
+};
+
 // Kernel launches (bn_kernels.hip), all on `stream`.  `part` holds
-// 2*partial_floats + grid floats of workspace.
+// 2*partial_floats + grid floats of workspace.  With `stats` set the
+// statistics pass is skipped and those partials are finalized instead.
 struct BnForwardArgs {
   const void* x;         // [R, C] bf16
   const void* identity;  // [R, C] bf16 or null
@@ -90,6 +107,7 @@ struct BnForwardArgs {
   float* invstd;  // [C]
   uint8_t* mask;  // [R*C/8], written iff relu
   float* part;
+  const BnPartials* stats = nullptr;
 };
 void launch_bn_forward(const BnPlan& p, const BnForwardArgs& a,
                        hipStream_t stream);
@@ -127,6 +145,7 @@ struct BnOperand {
   void* dx;             // [R, C] bf16, backward only
   float* dgamma;        // [C], backward only
   float* dbeta;         // [C], backward only
+  const BnPartials* stats = nullptr;  // forward only, as in BnForwardArgs
 };
 struct BnJoinArgs {
   BnOperand a, b;  // the block's bn3 and its downsample BatchNorm

@@ -1,0 +1,78 @@
+// Launch geometry of the 1x1 convolution with statistics: see conv1x1_plan.h.
+#include "conv1x1_plan.h"
+
+#include <algorithm>
+
+namespace cgx {
+namespace {
+
+// The shapes at which the native kernel plus finalize beat MIOpen's forward
+// plus bn_stats plus finalize in every run of an alternating measurement on
+// MI355X (slowest native run faster than the fastest MIOpen run; table in
+// benchmarks/RESULTS.md).  Measured at these row counts only, so only they go
+// native; the five other stride-1 1x1 problems of ResNet-50 at batch 256
+// (512->256, 1024->256, 1024->512, 512->2048, 2048->512), where W does not
+// stay in LDS, lost and stay with MIOpen.
+struct Measured {
+  int k, n;
+  int64_t rows;
+};
+constexpr Measured kNative[] = {
+    {64, 64, 802816},   {64, 256, 802816},  {256, 64, 802816},
+    {256, 128, 802816}, {128, 512, 200704}, {512, 128, 200704},
+    {256, 1024, 50176},
+};
+
+bool measured_faster(int64_t rows, int k, int n) {
+  for (const Measured& m : kNative)
+    if (m.k == k && m.n == n && m.rows == rows) return true;
+  return false;
+}
+
+bool pow2_in(int64_t v, int64_t lo, int64_t hi) {
+  return v >= lo && v <= hi && (v & (v - 1)) == 0;
+}
+
+}  // namespace
+
+Conv1x1Plan conv1x1_plan(int64_t rows, int64_t k, int64_t n,
+                         int max_workgroups) {
+  Conv1x1Plan p;
+  p.rows = rows;
+  p.eligible = pow2_in(k, 64, 2048) && pow2_in(n, 64, 2048) && rows >= 2 &&
+               rows <= kBnMaxRows;
+  if (!p.eligible) return p;
+  p.k = (int)k;
+  p.n = (int)n;
+  p.native = measured_faster(rows, p.k, p.n);
+
+  p.nt = std::min(p.n / 32, kConvMaxNt);
+  p.bn = 32 * p.nt;
+  p.ntiles = p.n / p.bn;
+  p.kc = p.k == 64 ? 64 : 128;
+  p.nchunks = p.k / p.kc;
+  p.resident = p.bn * p.k * 2 <= kConvWLdsBytes;
+  p.lds_bytes = p.bn * (p.resident ? p.k : p.kc) * 2 + kConvStageBytes;
+
+  p.row_tiles = (int)((rows + kConvTileRows - 1) / kConvTileRows);
+  // as many workgroups per CU as LDS and the registers allow (one wave per
+  // SIMD with 8 MFMA tiles per wave, two with 4, three with 2) ...
+  const int by_regs = p.nt == 8 ? 1 : p.nt == 4 ? 2 : 3;
+  const int per_cu = std::max(1, std::min(kConvLdsBytes / p.lds_bytes, by_regs));
+  int64_t splits = std::min<int64_t>(
+      p.row_tiles, std::max(1, kConvCus * per_cu / p.ntiles));
+  // ... while a partial row per split (8*N bytes and the counts) stays within
+  // 5% of the 2*R*N bytes of the output
+  splits = std::min(splits, std::max<int64_t>(1, rows / 82));
+  if (max_workgroups > 0)
+    splits = std::min<int64_t>(splits, std::max(1, max_workgroups / p.ntiles));
+  p.splits = (int)splits;
+  p.grid = p.ntiles * p.splits;
+  p.tiles_per_split = (p.row_tiles + p.splits - 1) / p.splits;
+  p.run = 16 * p.tiles_per_split;
+  p.pstride = 2 * p.n + p.ntiles;
+  p.partial_floats = (int64_t)p.splits * p.pstride;
+  return p;
+}
+
+}  // namespace cgx

@@ -1,0 +1,94 @@
+// Launch geometry of the 1x1-convolution forward that also produces the
+// BatchNorm partials of its output (conv1x1_kernels.hip).
+//
+// Pure host arithmetic, like bn_plan.h.  The convolution is the GEMM
+// Y[R, N] = X[R, K] * W[N, K]^T on a channels_last bf16 activation (R = N*H*W
+// rows) and the convolution's weight, both with K contiguous.
+//
+// A 256-thread workgroup owns `bn` = 32*nt output channels (nt tiles of the
+// 32x32x16 MFMA per wave) and walks 128-row tiles: wave w takes rows
+// 32*w .. 32*w+31 of the tile.  K is cut into chunks of `kc`; the W tile of the
+// workgroup ([bn, K], or one [bn, kc] chunk at a time where that does not fit)
+// sits in LDS, X goes from global memory straight into the MFMA operand
+// registers.  The grid is persistent: `splits` workgroups share one channel
+// tile, workgroup `split` walks row tiles split, split+splits, ... and keeps
+// each lane's running moments in registers across them, so a lane's run is
+// 16 rows per tile it visits.  Each workgroup writes one partial row
+// [mean(N) | M2(N) | count(ntiles)] of floats, which bn_stats_finalize merges
+// (BnPartials in bn_plan.h).
+#pragma once
+
+#include <cstdint>
+
+#include "bn_plan.h"
+
+namespace cgx {
+
+constexpr int kConvThreads = 256;
+constexpr int kConvTileRows = 128;        // 4 waves x 32 rows
+constexpr int kConvMaxNt = 8;             // 32-channel MFMA tiles per wave
+constexpr int kConvCus = 256;
+constexpr int kConvLdsBytes = 160 * 1024;
+constexpr int kConvWLdsBytes = 128 * 1024;  // most of it for a resident W tile
+constexpr int kConvStageBytes = 16 * 1024;  // 4 waves x [32 rows][64 channels]
+
+struct Conv1x1Plan {
+  int64_t rows = 0;  // R
+  int k = 0, n = 0;
+  bool eligible = false;
+  bool native = false;  // measured faster than MIOpen + bn_stats at this shape
+  int nt = 0;           // MFMA tiles across the workgroup's channels
+  int bn = 0;           // channels per workgroup, 32*nt
+  int ntiles = 0;       // workgroups across N
+  int kc = 0;           // K chunk: 64 if K == 64, else 128
+  int nchunks = 0;      // K / kc
+  bool resident = false;  // the whole [bn, K] W tile stays in LDS
+  int row_tiles = 0;      // ceil(R / 128)
+  int splits = 0;         // persistent workgroups per channel tile
+  int grid = 0;           // ntiles * splits
+  int tiles_per_split = 0;  // longest walk
+  int run = 0;              // per-lane run length: 16 * tiles_per_split
+  int lds_bytes = 0;
+  int pstride = 0;             // floats per partial row: 2*N + ntiles
+  int64_t partial_floats = 0;  // splits * pstride
+};
+
+// K and N powers of two in [64, 2048], 2 <= R <= 2^24 (as bn_plan).
+// `max_workgroups` > 0 caps the grid.
+Conv1x1Plan conv1x1_plan(int64_t rows, int64_t k, int64_t n,
+                         int max_workgroups = 0);
+
+// Workgroup `wg` owns channels [n0, n0 + bn) and, as its i-th tile, the rows
+// [row0, row1): the walk of the kernel and of the CPU replay.
+__host__ __device__ inline int conv1x1_ntile(const Conv1x1Plan& p, int wg) {
+  return wg % p.ntiles;
+}
+__host__ __device__ inline int conv1x1_split(const Conv1x1Plan& p, int wg) {
+  return wg / p.ntiles;
+}
+// the i-th row tile of a split
+__host__ __device__ inline int conv1x1_tile(const Conv1x1Plan& p, int split,
+                                            int i) {
+  return split + i * p.splits;
+}
+
+// The partials of a [splits, 2N + ntiles] buffer as the finalize reads them.
+inline BnPartials conv1x1_partials(const float* part, int n, int splits,
+                                   int ntiles) {
+  BnPartials q;
+  q.mean = part;
+  q.m2 = part + n;
+  q.cnt = part + 2 * n;
+  q.channels = n;
+  q.splits = splits;
+  q.tc = n / ntiles / 8;
+  q.pstride = q.cstride = 2 * n + ntiles;
+  return q;
+}
+
+// y[R, N] bf16 and part[splits, pstride] fp32 from x[R, K] and w[N, K] bf16;
+// every pointer 16-byte aligned.
+void launch_conv1x1_stats(const Conv1x1Plan& p, const void* x, const void* w,
+                          void* y, float* part, hipStream_t stream);
+
+}  // namespace cgx

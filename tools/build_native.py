@@ -17,11 +17,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SOURCES = [
     "csrc/quant_kernels.hip",
     "csrc/bn_kernels.hip",
+    "csrc/conv1x1_kernels.hip",
     "csrc/compress.cc",
     "csrc/config.cc",
     "csrc/registry.cc",
     "csrc/plan.cc",
     "csrc/bn_plan.cc",
+    "csrc/conv1x1_plan.cc",
     "csrc/phase_timer.cc",
     "csrc/engine.cc",
     "csrc/transport.cc",
@@ -33,7 +35,8 @@ SOURCES = [
 HEADERS = ["csrc/compress.h", "csrc/check.h", "csrc/config.h",
            "csrc/registry.h", "csrc/plan.h", "csrc/phase_timer.h",
            "csrc/engine.h", "csrc/backend.h", "csrc/transport.h",
-           "csrc/reducer.h", "csrc/bn_plan.h", "csrc/collectives.h"]
+           "csrc/reducer.h", "csrc/bn_plan.h", "csrc/collectives.h",
+           "csrc/bn_moments.h", "csrc/conv1x1_plan.h"]
 EXT_OUT = os.path.join(
     "torch_cgx_amd", "_C" + sysconfig.get_config_var("EXT_SUFFIX"))
 

@@ -11,7 +11,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from ..ops.fused_bn import bn_act, bn_act_pool
+from ..ops.fused_bn import bn_act, bn_act_pool, conv_bn_act
 
 
 class Bottleneck(nn.Module):
@@ -33,16 +33,18 @@ class Bottleneck(nn.Module):
 
     def forward(self, x):
         identity = x
-        out = bn_act(self.bn1, self.conv1(x))
+        # the stride-1 1x1 convolutions hand their BatchNorm the statistics of
+        # their output where the native GEMM is the faster one
+        # (benchmarks/RESULTS.md)
+        out = conv_bn_act(self.conv1, self.bn1, x)
         out = bn_act(self.bn2, self.conv2(out))
-        out = self.conv3(out)
         if self.downsample is not None:
             # the downsample BatchNorm is the second operand of bn3's sweeps:
             # its output and its gradient never go through memory
-            # (benchmarks/RESULTS.md)
             conv, bn = self.downsample[0], self.downsample[1]
-            return bn_act(self.bn3, out, conv(x), identity_bn=bn)
-        return bn_act(self.bn3, out, identity)
+            return conv_bn_act(self.conv3, self.bn3, out, identity,
+                               identity_conv=conv, identity_bn=bn)
+        return conv_bn_act(self.conv3, self.bn3, out, identity)
 
 
 class ResNet(nn.Module):

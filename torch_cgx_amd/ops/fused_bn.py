@@ -19,7 +19,17 @@ BatchNorms at once and its dx pass writes both input gradients.
 tensor and one byte per pooled element (which of the nine window positions
 won), and the backward builds each pixel's gradient from those.
 
-``CGX_FUSED_BN=0`` switches the native paths off.
+``conv_bn_act(conv, bn, x, ...)`` is ``bn_act(bn, conv(x), ...)``.  Where
+``conv`` is a 1x1 / stride 1 convolution at a shape the plan
+(csrc/conv1x1_plan.cc) has measured faster, the native GEMM kernel
+(csrc/conv1x1_kernels.hip) computes it and hands the BatchNorm the
+per-channel partial statistics of its output, so the statistics pass over
+that output is skipped.  ``identity_conv`` does the same for the downsample
+convolution of a join.  ``CGX_NATIVE_CONV1X1=0`` switches this off,
+``CGX_NATIVE_CONV1X1=all`` takes every shape the kernel accepts, measured
+faster or not.
+
+``CGX_FUSED_BN=0`` switches all native paths off.
 """
 
 from __future__ import annotations
@@ -35,10 +45,10 @@ from .. import _C
 class _BnAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, identity, weight, bias, running_mean, running_var,
-                momentum, eps, relu):
+                momentum, eps, relu, part):
         out, mean, invstd, mask = _C.bn_act_forward(
             x, identity, weight, bias, running_mean, running_var, momentum,
-            eps, relu)
+            eps, relu, part)
         ctx.save_for_backward(x, mean, invstd, weight, mask)
         ctx.has_identity = identity is not None
         return out
@@ -48,17 +58,19 @@ class _BnAct(torch.autograd.Function):
         x, mean, invstd, weight, mask = ctx.saved_tensors
         dx, dgamma, dbeta, didentity = _C.bn_act_backward(
             dy, x, mean, invstd, weight, mask, ctx.has_identity)
-        return (dx, didentity, dgamma, dbeta, None, None, None, None, None)
+        return (dx, didentity, dgamma, dbeta, None, None, None, None, None,
+                None)
 
 
 class _BnActJoin(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, xd, weight, bias, running_mean, running_var, momentum,
                 eps, weightd, biasd, running_meand, running_vard, momentumd,
-                epsd, relu):
+                epsd, relu, part, partd):
         out, mean, invstd, meand, invstdd, mask = _C.bn_act2_forward(
             x, xd, weight, bias, running_mean, running_var, momentum, eps,
-            weightd, biasd, running_meand, running_vard, momentumd, epsd, relu)
+            weightd, biasd, running_meand, running_vard, momentumd, epsd, relu,
+            part, partd)
         ctx.save_for_backward(x, xd, mean, invstd, weight, meand, invstdd,
                               weightd, mask)
         return out
@@ -70,7 +82,7 @@ class _BnActJoin(torch.autograd.Function):
         dx, dxd, dgamma, dbeta, dgammad, dbetad = _C.bn_act2_backward(
             dy, x, xd, mean, invstd, weight, meand, invstdd, weightd, mask)
         return (dx, dxd, dgamma, dbeta, None, None, None, None, dgammad,
-                dbetad, None, None, None, None, None)
+                dbetad, None, None, None, None, None, None, None)
 
 
 class _BnActPool(torch.autograd.Function):
@@ -116,26 +128,113 @@ def _bn_args(bn):
 
 def bn_act(bn: torch.nn.BatchNorm2d, x: torch.Tensor,
            identity: torch.Tensor = None, relu: bool = True,
-           identity_bn: torch.nn.BatchNorm2d = None) -> torch.Tensor:
+           identity_bn: torch.nn.BatchNorm2d = None,
+           part: torch.Tensor = None,
+           identity_part: torch.Tensor = None) -> torch.Tensor:
     """``relu(bn(x) + identity)``; ``identity`` and ``relu`` are optional.
-    With ``identity_bn`` it is ``relu(bn(x) + identity_bn(identity))``."""
+    With ``identity_bn`` it is ``relu(bn(x) + identity_bn(identity))``.
+    ``part`` / ``identity_part`` are the statistics partials that came with
+    ``x`` / ``identity`` from the native 1x1 convolution, if it produced
+    them."""
     if identity_bn is not None:
         if _native(bn, x, identity) and _native(identity_bn, identity, x):
             bn.num_batches_tracked.add_(1)
             identity_bn.num_batches_tracked.add_(1)
             return _BnActJoin.apply(x, identity, *_bn_args(bn),
-                                    *_bn_args(identity_bn), relu)
+                                    *_bn_args(identity_bn), relu, part,
+                                    identity_part)
         out = bn(x) + identity_bn(identity)
         return F.relu(out, inplace=True) if relu else out
     if _native(bn, x, identity):
         bn.num_batches_tracked.add_(1)
-        return _BnAct.apply(x, identity, *_bn_args(bn), relu)
+        return _BnAct.apply(x, identity, *_bn_args(bn), relu, part)
     out = bn(x)
     if identity is not None:
         out = out + identity
     if relu:
         out = F.relu(out, inplace=True)
     return out
+
+
+class _Conv1x1Stats(torch.autograd.Function):
+    """The 1x1 convolution and the BatchNorm partials of its output; the
+    backward is the stock convolution backward on the same operands."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
+    def forward(ctx, x, weight):
+        y, part = _C.conv1x1_stats(x, weight)
+        ctx.save_for_backward(x, weight)
+        ctx.mark_non_differentiable(part)
+        return y, part
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dy, _dpart):
+        x, weight = ctx.saved_tensors
+        dx, dw, _ = torch.ops.aten.convolution_backward(
+            dy, x, weight, None, (1, 1), (0, 0), (1, 1), False, (0, 0), 1,
+            (ctx.needs_input_grad[0], ctx.needs_input_grad[1], False))
+        return dx, dw
+
+
+def native_conv1x1_mode() -> str:
+    """"0": off; "all": every eligible shape; else the plan decides."""
+    if not fused_bn_enabled():
+        return "0"
+    return os.environ.get("CGX_NATIVE_CONV1X1", "1")
+
+
+def _conv1x1_native(conv, bn, x) -> bool:
+    mode = native_conv1x1_mode()
+    if mode == "0":
+        return False
+    if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == (1, 1)
+            and conv.stride == (1, 1) and conv.padding == (0, 0)
+            and conv.dilation == (1, 1) and conv.groups == 1
+            and conv.bias is None and conv.padding_mode == "zeros"):
+        return False
+    if not (bn.training and bn.track_running_stats
+            and bn.momentum is not None and bn.weight is not None
+            and bn.bias is not None and bn.weight.dtype == torch.float32):
+        return False
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16
+            and _C.bn_eligible(x)):
+        return False
+    w = conv.weight
+    # under bf16 autocast the fp32 weight reaches the kernel as bf16
+    autocast = (torch.is_autocast_enabled("cuda")
+                and torch.get_autocast_dtype("cuda") == torch.bfloat16)
+    if not (w.device == x.device and w.shape[1] == x.shape[1]
+            and (w.dtype == torch.bfloat16
+                 or (autocast and w.dtype == torch.float32))):
+        return False
+    if w.dtype == torch.bfloat16 and not _C.conv1x1_eligible(x, w):
+        return False  # e.g. a weight view that is not dense or not aligned
+    plan = _C.conv1x1_plan(x.numel() // x.shape[1], x.shape[1], w.shape[0])
+    return plan["eligible"] and (plan["native"] or mode == "all")
+
+
+def _conv(conv, bn, x):
+    """``conv(x)`` and the partials for ``bn``, or None where the stock
+    convolution ran."""
+    if _conv1x1_native(conv, bn, x):
+        return _Conv1x1Stats.apply(x, conv.weight)
+    return conv(x), None
+
+
+def conv_bn_act(conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d,
+                x: torch.Tensor, identity: torch.Tensor = None,
+                relu: bool = True, identity_conv: torch.nn.Conv2d = None,
+                identity_bn: torch.nn.BatchNorm2d = None) -> torch.Tensor:
+    """``relu(bn(conv(x)) + identity)``, or with ``identity_conv`` and
+    ``identity_bn`` ``relu(bn(conv(x)) + identity_bn(identity_conv(identity)))``."""
+    y, part = _conv(conv, bn, x)
+    if identity_conv is None:
+        return bn_act(bn, y, identity, relu, part=part)
+    yd, partd = _conv(identity_conv, identity_bn, identity)
+    return bn_act(bn, y, yd, relu, identity_bn=identity_bn, part=part,
+                  identity_part=partd)
 
 
 def _pool_is_3x3_s2_p1(pool) -> bool:
