@@ -1011,10 +1011,7 @@ py::dict py_conv1x1_plan(int64_t rows, int64_t k, int64_t n,
 // Test seam: replay the kernel's tile walk on the host.  Entry [wg, i] holds
 // (row0, row1, n0, n1) of the i-th tile of workgroup wg: the rows it stores
 // and counts and its channels; -1 once it has run out of tiles.
-at::Tensor py_conv1x1_walk(int64_t rows, int64_t k, int64_t n,
-                           int64_t max_workgroups) {
-  const Conv1x1Plan p = conv1x1_plan(rows, k, n, (int)max_workgroups);
-  TORCH_CHECK(p.eligible, "conv1x1_walk: shape is not eligible");
+at::Tensor conv1x1_walk_of(const Conv1x1Plan& p) {
   auto out = at::full({p.grid, p.tiles_per_split, 4}, -1,
                       at::TensorOptions().dtype(at::kLong));
   int64_t* o = out.data_ptr<int64_t>();
@@ -1031,6 +1028,93 @@ at::Tensor py_conv1x1_walk(int64_t rows, int64_t k, int64_t n,
     }
   }
   return out;
+}
+
+at::Tensor py_conv1x1_walk(int64_t rows, int64_t k, int64_t n,
+                           int64_t max_workgroups) {
+  const Conv1x1Plan p = conv1x1_plan(rows, k, n, (int)max_workgroups);
+  TORCH_CHECK(p.eligible, "conv1x1_walk: shape is not eligible");
+  return conv1x1_walk_of(p);
+}
+
+// ---- 1x1 convolution backward-data with the skip gradient added ------------
+
+int clamp_workgroups(int64_t max_workgroups) {
+  return (int)std::min<int64_t>(max_workgroups, 1 << 20);
+}
+
+// dy as the BatchNorm kernels take it, the convolution's dense bf16
+// [N, K, 1, 1] weight, and a skip gradient, if any, of dX's shape and layout.
+bool py_conv1x1_bwd_eligible(const at::Tensor& dy, const at::Tensor& weight,
+                             const c10::optional<at::Tensor>& skip) {
+  if (!(bn_tensor_ok(dy) && weight.is_cuda() &&
+        weight.device() == dy.device() &&
+        weight.scalar_type() == at::kBFloat16 && weight.dim() == 4 &&
+        weight.size(0) == dy.size(1) && weight.size(2) == 1 &&
+        weight.size(3) == 1 && weight.is_contiguous() &&
+        reinterpret_cast<uintptr_t>(weight.data_ptr()) % 16 == 0 &&
+        conv1x1_bwd_plan(dy.numel() / dy.size(1), weight.size(1),
+                         weight.size(0), skip.has_value())
+            .eligible))
+    return false;
+  if (!skip.has_value()) return true;
+  const at::Tensor& s = *skip;
+  return s.dim() == 4 && s.size(0) == dy.size(0) &&
+         s.size(1) == weight.size(1) && s.size(2) == dy.size(2) &&
+         s.size(3) == dy.size(3) && s.device() == dy.device() &&
+         bn_tensor_ok(s);
+}
+
+// Gradient of conv2d(x, weight) for x, plus `skip`: (dy, weight, skip) -> dx
+at::Tensor py_conv1x1_bwd_data(const at::Tensor& dy, const at::Tensor& weight,
+                               const c10::optional<at::Tensor>& skip,
+                               int64_t max_workgroups) {
+  TORCH_CHECK(max_workgroups >= 0, "conv1x1_bwd_data: max_workgroups >= 0");
+  TORCH_CHECK(py_conv1x1_bwd_eligible(dy, weight, skip),
+              "conv1x1_bwd_data: dy, weight or skip is not eligible");
+  const Conv1x1Plan p = conv1x1_bwd_plan(
+      dy.numel() / dy.size(1), weight.size(1), weight.size(0),
+      skip.has_value(), clamp_workgroups(max_workgroups));
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dy.device().index());
+  auto dx = at::empty({dy.size(0), p.n, dy.size(2), dy.size(3)}, dy.options(),
+                      at::MemoryFormat::ChannelsLast);
+  launch_conv1x1_bwd_data(p, dy.data_ptr(), weight.data_ptr(),
+                          skip.has_value() ? skip->data_ptr() : nullptr,
+                          dx.data_ptr(), bn_stream(dy));
+  return dx;
+}
+
+// The keys of conv1x1_plan that the backward has, with the same meaning:
+// tile_channels / ntiles are over dX's K channels, k_chunk(s) over dY's N.
+py::dict py_conv1x1_bwd_plan(int64_t rows, int64_t k, int64_t n, bool with_add,
+                             int64_t max_workgroups) {
+  const Conv1x1Plan p =
+      conv1x1_bwd_plan(rows, k, n, with_add, clamp_workgroups(max_workgroups));
+  py::dict d;
+  d["eligible"] = p.eligible;
+  d["native"] = p.native;
+  d["threads"] = kConvThreads;
+  d["tile_rows"] = kConvTileRows;
+  d["mfma_tiles"] = p.nt;
+  d["tile_channels"] = p.bn;
+  d["ntiles"] = p.ntiles;
+  d["k_chunk"] = p.kc;
+  d["k_chunks"] = p.nchunks;
+  d["resident"] = p.resident;
+  d["row_tiles"] = p.row_tiles;
+  d["splits"] = p.splits;
+  d["grid"] = p.grid;
+  d["tiles_per_split"] = p.tiles_per_split;
+  d["lds_bytes"] = p.lds_bytes;
+  return d;
+}
+
+at::Tensor py_conv1x1_bwd_walk(int64_t rows, int64_t k, int64_t n,
+                               bool with_add, int64_t max_workgroups) {
+  const Conv1x1Plan p =
+      conv1x1_bwd_plan(rows, k, n, with_add, clamp_workgroups(max_workgroups));
+  TORCH_CHECK(p.eligible, "conv1x1_bwd_walk: shape is not eligible");
+  return conv1x1_walk_of(p);
 }
 
 void py_register_layer(int64_t bucket_idx, int64_t layer_idx, int64_t numel,
@@ -1234,6 +1318,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("n"), py::arg("max_workgroups") = 0,
         "Test seam: [grid, tiles_per_split, 4] int64, (row0, row1, n0, n1) "
         "of every tile each workgroup visits (-1: none).");
+  m.def("conv1x1_bwd_data", &cgx::py_conv1x1_bwd_data, py::arg("dy"),
+        py::arg("weight"), py::arg("skip") = py::none(),
+        py::arg("max_workgroups") = 0,
+        "Input gradient of conv2d(x, weight) for a 1x1 / stride 1 convolution "
+        "on channels_last bf16 tensors, plus `skip` (a bf16 channels_last "
+        "tensor of dx's shape) where given: dx = bf16(dy * W + skip), rounded "
+        "once.  `skip` is not written.");
+  m.def("conv1x1_bwd_eligible", &cgx::py_conv1x1_bwd_eligible, py::arg("dy"),
+        py::arg("weight"), py::arg("skip") = py::none(),
+        "True where conv1x1_bwd_data takes (dy, weight, skip).");
+  m.def("conv1x1_bwd_plan", &cgx::py_conv1x1_bwd_plan, py::arg("rows"),
+        py::arg("k"), py::arg("n"), py::arg("with_add") = false,
+        py::arg("max_workgroups") = 0,
+        "The launch geometry of conv1x1_bwd_data for dx [rows, k] from dy "
+        "[rows, n], and `native`: whether the model uses it for this problem.");
+  m.def("conv1x1_bwd_walk", &cgx::py_conv1x1_bwd_walk, py::arg("rows"),
+        py::arg("k"), py::arg("n"), py::arg("with_add") = false,
+        py::arg("max_workgroups") = 0,
+        "Test seam: conv1x1_walk for the plan of conv1x1_bwd_plan; channels "
+        "are dx's.");
   m.def("bn_act2_backward", &cgx::py_bn_act2_backward,
         "Backward of bn_act2_forward: (dy, x3, xd, mean3, invstd3, weight3, "
         "meand, invstdd, weightd, mask) -> (dx3, dxd, dgamma3, dbeta3, "

@@ -33,6 +33,59 @@ bool pow2_in(int64_t v, int64_t lo, int64_t hi) {
   return v >= lo && v <= hi && (v & (v - 1)) == 0;
 }
 
+// The backward-data problems (dX K wide, dY N wide, with or without the skip
+// gradient added) that met the same rule against MIOpen's backward-data plus,
+// with a skip gradient, the bf16 add that follows it (benchmarks/RESULTS.md):
+// the eight of ResNet-50's twelve at batch 256 whose W^T tile stays in LDS.
+// 1024->512 and 2048->512 with the add, 256->1024 and 512->2048 without, lost.
+struct MeasuredBwd {
+  int k, n;
+  int64_t rows;
+  bool with_add;
+};
+constexpr MeasuredBwd kNativeBwd[] = {
+    {64, 64, 802816, true},    {256, 64, 802816, true},
+    {256, 128, 802816, true},  {512, 128, 200704, true},
+    {512, 256, 200704, true},  {1024, 256, 50176, true},
+    {64, 256, 802816, false},  {128, 512, 200704, false},
+};
+
+bool measured_faster_bwd(int64_t rows, int k, int n, bool with_add) {
+  for (const MeasuredBwd& m : kNativeBwd)
+    if (m.k == k && m.n == n && m.rows == rows && m.with_add == with_add)
+      return true;
+  return false;
+}
+
+// The tiles of a GEMM with p.k contracted and p.n produced; `stage_bytes` of
+// LDS go to the waves' output strips.
+void tile_geometry(Conv1x1Plan& p, int stage_bytes) {
+  p.nt = std::min(p.n / 32, kConvMaxNt);
+  p.bn = 32 * p.nt;
+  p.ntiles = p.n / p.bn;
+  p.kc = p.k == 64 ? 64 : 128;
+  p.nchunks = p.k / p.kc;
+  p.resident = p.bn * p.k * 2 <= kConvWLdsBytes;
+  p.lds_bytes = p.bn * (p.resident ? p.k : p.kc) * 2 + stage_bytes;
+  p.row_tiles = (int)((p.rows + kConvTileRows - 1) / kConvTileRows);
+}
+
+// as many workgroups per CU as LDS and the registers (`by_regs` waves per
+// SIMD) allow
+int64_t splits_by_occupancy(const Conv1x1Plan& p, int by_regs) {
+  const int per_cu = std::max(1, std::min(kConvLdsBytes / p.lds_bytes, by_regs));
+  return std::min<int64_t>(p.row_tiles,
+                           std::max(1, kConvCus * per_cu / p.ntiles));
+}
+
+void set_grid(Conv1x1Plan& p, int64_t splits, int max_workgroups) {
+  if (max_workgroups > 0)
+    splits = std::min<int64_t>(splits, std::max(1, max_workgroups / p.ntiles));
+  p.splits = (int)splits;
+  p.grid = p.ntiles * p.splits;
+  p.tiles_per_split = (p.row_tiles + p.splits - 1) / p.splits;
+}
+
 }  // namespace
 
 Conv1x1Plan conv1x1_plan(int64_t rows, int64_t k, int64_t n,
@@ -45,33 +98,38 @@ Conv1x1Plan conv1x1_plan(int64_t rows, int64_t k, int64_t n,
   p.k = (int)k;
   p.n = (int)n;
   p.native = measured_faster(rows, p.k, p.n);
-
-  p.nt = std::min(p.n / 32, kConvMaxNt);
-  p.bn = 32 * p.nt;
-  p.ntiles = p.n / p.bn;
-  p.kc = p.k == 64 ? 64 : 128;
-  p.nchunks = p.k / p.kc;
-  p.resident = p.bn * p.k * 2 <= kConvWLdsBytes;
-  p.lds_bytes = p.bn * (p.resident ? p.k : p.kc) * 2 + kConvStageBytes;
-
-  p.row_tiles = (int)((rows + kConvTileRows - 1) / kConvTileRows);
-  // as many workgroups per CU as LDS and the registers allow (one wave per
-  // SIMD with 8 MFMA tiles per wave, two with 4, three with 2) ...
+  tile_geometry(p, kConvStageBytes);
+  // no more splits than keep a partial row per split (8*N bytes and the
+  // counts) within 5% of the 2*R*N bytes of the output
+  // one wave per SIMD with 8 MFMA tiles per wave, two with 4, three with 2
   const int by_regs = p.nt == 8 ? 1 : p.nt == 4 ? 2 : 3;
-  const int per_cu = std::max(1, std::min(kConvLdsBytes / p.lds_bytes, by_regs));
-  int64_t splits = std::min<int64_t>(
-      p.row_tiles, std::max(1, kConvCus * per_cu / p.ntiles));
-  // ... while a partial row per split (8*N bytes and the counts) stays within
-  // 5% of the 2*R*N bytes of the output
-  splits = std::min(splits, std::max<int64_t>(1, rows / 82));
-  if (max_workgroups > 0)
-    splits = std::min<int64_t>(splits, std::max(1, max_workgroups / p.ntiles));
-  p.splits = (int)splits;
-  p.grid = p.ntiles * p.splits;
-  p.tiles_per_split = (p.row_tiles + p.splits - 1) / p.splits;
+  set_grid(p,
+           std::min(splits_by_occupancy(p, by_regs),
+                    std::max<int64_t>(1, rows / 82)),
+           max_workgroups);
   p.run = 16 * p.tiles_per_split;
   p.pstride = 2 * p.n + p.ntiles;
   p.partial_floats = (int64_t)p.splits * p.pstride;
+  return p;
+}
+
+Conv1x1Plan conv1x1_bwd_plan(int64_t rows, int64_t k, int64_t n, bool with_add,
+                             int max_workgroups) {
+  Conv1x1Plan p;
+  p.rows = rows;
+  p.eligible = pow2_in(k, 64, 2048) && pow2_in(n, 64, 2048) && rows >= 2 &&
+               rows <= kBnMaxRows;
+  if (!p.eligible) return p;
+  p.k = (int)n;  // contracted: the width of dY
+  p.n = (int)k;  // produced: the width of dX
+  p.native = measured_faster_bwd(rows, (int)k, (int)n, with_add);
+  tile_geometry(p, kConvBwdStageBytes);
+  // without the moments the kernel needs fewer registers than the forward:
+  // two waves per SIMD with 8 MFMA tiles, three with 4, four with 2, and one
+  // / two / two where W is staged chunk by chunk
+  const int by_regs = p.resident ? (p.nt == 8 ? 2 : p.nt == 4 ? 3 : 4)
+                                 : (p.nt == 8 ? 1 : 2);
+  set_grid(p, splits_by_occupancy(p, by_regs), max_workgroups);
   return p;
 }
 

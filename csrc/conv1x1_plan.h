@@ -31,6 +31,9 @@ constexpr int kConvCus = 256;
 constexpr int kConvLdsBytes = 160 * 1024;
 constexpr int kConvWLdsBytes = 128 * 1024;  // most of it for a resident W tile
 constexpr int kConvStageBytes = 16 * 1024;  // 4 waves x [32 rows][64 channels]
+// backward-data: the strips hold fp32, so that the skip gradient is added
+// before the one rounding
+constexpr int kConvBwdStageBytes = 32 * 1024;
 
 struct Conv1x1Plan {
   int64_t rows = 0;  // R
@@ -57,6 +60,18 @@ struct Conv1x1Plan {
 // `max_workgroups` > 0 caps the grid.
 Conv1x1Plan conv1x1_plan(int64_t rows, int64_t k, int64_t n,
                          int max_workgroups = 0);
+
+// Backward-data of the same convolution, dX[R, K] = dY[R, N] * W[N, K], with
+// the skip gradient of a residual fork optionally added in the epilogue
+// (conv1x1_bwd_data in conv1x1_kernels.hip).  It is the forward GEMM with the
+// roles of k and n exchanged: in the returned plan `k` is the contracted
+// width (the convolution's N, the channels of dY) and `n` the produced one
+// (the convolution's K, the channels of dX); `bn`, `ntiles` and the walk are
+// over dX's channels.  There are no partials: run, pstride and partial_floats
+// stay 0.  `native` comes from this problem's own measurement and depends on
+// `with_add`.
+Conv1x1Plan conv1x1_bwd_plan(int64_t rows, int64_t k, int64_t n, bool with_add,
+                             int max_workgroups = 0);
 
 // Workgroup `wg` owns channels [n0, n0 + bn) and, as its i-th tile, the rows
 // [row0, row1): the walk of the kernel and of the CPU replay.
@@ -90,5 +105,11 @@ inline BnPartials conv1x1_partials(const float* part, int n, int splits,
 // every pointer 16-byte aligned.
 void launch_conv1x1_stats(const Conv1x1Plan& p, const void* x, const void* w,
                           void* y, float* part, hipStream_t stream);
+
+// dx[R, K] = bf16(dy[R, N] * w[N, K] + skip[R, K]) for a plan of
+// conv1x1_bwd_plan; skip may be null.  Every pointer 16-byte aligned.
+void launch_conv1x1_bwd_data(const Conv1x1Plan& p, const void* dy,
+                             const void* w, const void* skip, void* dx,
+                             hipStream_t stream);
 
 }  // namespace cgx

@@ -11,7 +11,8 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from ..ops.fused_bn import bn_act, bn_act_pool, conv_bn_act
+from ..ops.fused_bn import (bn_act, bn_act_pool, conv_bn_act,
+                            conv_bn_act_fork)
 
 
 class Bottleneck(nn.Module):
@@ -32,11 +33,11 @@ class Bottleneck(nn.Module):
         self.stride = stride
 
     def forward(self, x):
-        identity = x
         # the stride-1 1x1 convolutions hand their BatchNorm the statistics of
         # their output where the native GEMM is the faster one
-        # (benchmarks/RESULTS.md)
-        out = conv_bn_act(self.conv1, self.bn1, x)
+        # (benchmarks/RESULTS.md); the skip path leaves from conv1, whose
+        # backward-data GEMM then adds that path's gradient in its epilogue
+        out, identity = conv_bn_act_fork(self.conv1, self.bn1, x)
         out = bn_act(self.bn2, self.conv2(out))
         if self.downsample is not None:
             # the downsample BatchNorm is the second operand of bn3's sweeps:

@@ -29,6 +29,16 @@ convolution of a join.  ``CGX_NATIVE_CONV1X1=0`` switches this off,
 ``CGX_NATIVE_CONV1X1=all`` takes every shape the kernel accepts, measured
 faster or not.
 
+The input gradient of such a convolution is the same GEMM with the roles of
+its channels exchanged (``_C.conv1x1_bwd_data``), taken where its own table
+in the plan has measured it faster than the stock backward-data.
+``conv_bn_act_fork`` is ``conv_bn_act`` at the input of a residual block: it
+also returns the tensor the skip path continues from, and the gradient
+arriving over that path is then added in the GEMM's epilogue, not by
+autograd in a pass of its own.  The weight gradient stays the stock one.
+``CGX_NATIVE_CONV1X1_BWD=0|1|all`` works like the forward switch and is off
+wherever that one is.
+
 ``CGX_FUSED_BN=0`` switches all native paths off.
 """
 
@@ -178,6 +188,57 @@ class _Conv1x1Stats(torch.autograd.Function):
         return dx, dw
 
 
+class _Conv1x1Fork(torch.autograd.Function):
+    """``(y, part, skip) = f(x, weight)``: the 1x1 convolution, native with
+    partials or stock with ``part`` None as ``native_fwd`` says, and with
+    ``fork`` its input once more as ``skip``, for the residual path to go on
+    from.  The backward then receives the gradients of both at once, and the
+    native backward-data GEMM adds the skip gradient in its epilogue instead
+    of autograd in a pass of its own.  The weight gradient is the stock one."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
+    def forward(ctx, x, weight, native_fwd, fork):
+        if native_fwd:
+            y, part = _C.conv1x1_stats(x, weight)
+            ctx.mark_non_differentiable(part)
+        else:
+            y, part = F.conv2d(x, weight), None
+        ctx.save_for_backward(x, weight)
+        # an unused output arrives as None, not as a tensor of zeros to add
+        ctx.set_materialize_grads(False)
+        return y, part, (x.view_as(x) if fork else None)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dy, _dpart, dskip):
+        x, weight = ctx.saved_tensors
+        dx = dw = None
+        if dy is not None and ctx.needs_input_grad[1]:
+            dw = _conv1x1_backward(dy, x, weight, (False, True, False))[1]
+        if ctx.needs_input_grad[0]:
+            dx = dskip if dy is None else _conv1x1_dx(dy, x, weight, dskip)
+        return dx, dw, None, None
+
+
+def _conv1x1_backward(dy, x, weight, mask):
+    return torch.ops.aten.convolution_backward(
+        dy, x, weight, None, (1, 1), (0, 0), (1, 1), False, (0, 0), 1, mask)
+
+
+def _conv1x1_dx(dy, x, weight, dskip):
+    """The input gradient plus ``dskip`` (or None): one native GEMM where the
+    plan has measured it faster, else the stock backward-data and a ``+``."""
+    mode = native_conv1x1_bwd_mode()
+    if mode != "0" and _C.conv1x1_bwd_eligible(dy, weight, dskip):
+        plan = _C.conv1x1_bwd_plan(x.numel() // x.shape[1], x.shape[1],
+                                   weight.shape[0], dskip is not None)
+        if plan["native"] or mode == "all":
+            return _C.conv1x1_bwd_data(dy, weight, dskip)
+    dx = _conv1x1_backward(dy, x, weight, (True, False, False))[0]
+    return dx if dskip is None else dx + dskip
+
+
 def native_conv1x1_mode() -> str:
     """"0": off; "all": every eligible shape; else the plan decides."""
     if not fused_bn_enabled():
@@ -185,22 +246,31 @@ def native_conv1x1_mode() -> str:
     return os.environ.get("CGX_NATIVE_CONV1X1", "1")
 
 
-def _conv1x1_native(conv, bn, x) -> bool:
-    mode = native_conv1x1_mode()
-    if mode == "0":
-        return False
+def native_conv1x1_bwd_mode() -> str:
+    """As native_conv1x1_mode, for the backward-data GEMM; off wherever the
+    forward switch is."""
+    if native_conv1x1_mode() == "0":
+        return "0"
+    return os.environ.get("CGX_NATIVE_CONV1X1_BWD", "1")
+
+
+def _conv1x1_shape(conv, bn, x):
+    """(rows, K, N) where everything but the plan admits the native kernels,
+    else None."""
+    if native_conv1x1_mode() == "0":
+        return None
     if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == (1, 1)
             and conv.stride == (1, 1) and conv.padding == (0, 0)
             and conv.dilation == (1, 1) and conv.groups == 1
             and conv.bias is None and conv.padding_mode == "zeros"):
-        return False
+        return None
     if not (bn.training and bn.track_running_stats
             and bn.momentum is not None and bn.weight is not None
             and bn.bias is not None and bn.weight.dtype == torch.float32):
-        return False
+        return None
     if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16
             and _C.bn_eligible(x)):
-        return False
+        return None
     w = conv.weight
     # under bf16 autocast the fp32 weight reaches the kernel as bf16
     autocast = (torch.is_autocast_enabled("cuda")
@@ -208,19 +278,43 @@ def _conv1x1_native(conv, bn, x) -> bool:
     if not (w.device == x.device and w.shape[1] == x.shape[1]
             and (w.dtype == torch.bfloat16
                  or (autocast and w.dtype == torch.float32))):
-        return False
+        return None
     if w.dtype == torch.bfloat16 and not _C.conv1x1_eligible(x, w):
-        return False  # e.g. a weight view that is not dense or not aligned
-    plan = _C.conv1x1_plan(x.numel() // x.shape[1], x.shape[1], w.shape[0])
+        return None  # e.g. a weight view that is not dense or not aligned
+    return x.numel() // x.shape[1], x.shape[1], w.shape[0]
+
+
+def _conv1x1_native(shape) -> bool:
+    plan = _C.conv1x1_plan(*shape)
+    return plan["eligible"] and (plan["native"]
+                                 or native_conv1x1_mode() == "all")
+
+
+def _conv1x1_bwd_native(shape, with_add) -> bool:
+    mode = native_conv1x1_bwd_mode()
+    if mode == "0":
+        return False
+    plan = _C.conv1x1_bwd_plan(*shape, with_add)
     return plan["eligible"] and (plan["native"] or mode == "all")
 
 
-def _conv(conv, bn, x):
-    """``conv(x)`` and the partials for ``bn``, or None where the stock
-    convolution ran."""
-    if _conv1x1_native(conv, bn, x):
-        return _Conv1x1Stats.apply(x, conv.weight)
-    return conv(x), None
+def _conv(conv, bn, x, fork=False):
+    """``(conv(x), part, skip)``: ``part`` are the partials for ``bn``, or
+    None where the stock convolution ran; ``skip`` is what a residual path
+    continues from instead of ``x``.  It is ``x`` itself unless ``fork`` is
+    set and the native backward-data is to add the path's gradient."""
+    shape = _conv1x1_shape(conv, bn, x)
+    if shape is None:
+        return conv(x), None, x
+    fwd = _conv1x1_native(shape)
+    if torch.is_grad_enabled():
+        fork = fork and _conv1x1_bwd_native(shape, True)
+        if fork or _conv1x1_bwd_native(shape, False):
+            y, part, skip = _Conv1x1Fork.apply(x, conv.weight, fwd, fork)
+            return y, part, (skip if fork else x)
+    if fwd:
+        return _Conv1x1Stats.apply(x, conv.weight) + (x,)
+    return conv(x), None, x
 
 
 def conv_bn_act(conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d,
@@ -229,12 +323,22 @@ def conv_bn_act(conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d,
                 identity_bn: torch.nn.BatchNorm2d = None) -> torch.Tensor:
     """``relu(bn(conv(x)) + identity)``, or with ``identity_conv`` and
     ``identity_bn`` ``relu(bn(conv(x)) + identity_bn(identity_conv(identity)))``."""
-    y, part = _conv(conv, bn, x)
+    y, part, _ = _conv(conv, bn, x)
     if identity_conv is None:
         return bn_act(bn, y, identity, relu, part=part)
-    yd, partd = _conv(identity_conv, identity_bn, identity)
+    yd, partd, _ = _conv(identity_conv, identity_bn, identity)
     return bn_act(bn, y, yd, relu, identity_bn=identity_bn, part=part,
                   identity_part=partd)
+
+
+def conv_bn_act_fork(conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d,
+                     x: torch.Tensor, relu: bool = True):
+    """``(relu(bn(conv(x))), skip)`` at the input of a residual block:
+    ``skip`` has the value of ``x`` and is what the skip path must use in its
+    place, so that the path's gradient reaches the convolution's backward
+    (``_Conv1x1Fork``).  Where that does not apply ``skip`` is ``x``."""
+    y, part, skip = _conv(conv, bn, x, fork=True)
+    return bn_act(bn, y, None, relu, part=part), skip
 
 
 def _pool_is_3x3_s2_p1(pool) -> bool:
