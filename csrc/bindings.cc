@@ -1117,6 +1117,87 @@ at::Tensor py_conv1x1_bwd_walk(int64_t rows, int64_t k, int64_t n,
   return conv1x1_walk_of(p);
 }
 
+// ---- 1x1 convolution backward-weights --------------------------------------
+
+// dy and x as the BatchNorm kernels take them, of one batch and image size.
+bool py_conv1x1_wrw_eligible(const at::Tensor& dy, const at::Tensor& x) {
+  return bn_tensor_ok(dy) && bn_tensor_ok(x) && x.device() == dy.device() &&
+         x.size(0) == dy.size(0) && x.size(2) == dy.size(2) &&
+         x.size(3) == dy.size(3) &&
+         conv1x1_wrw_plan(dy.numel() / dy.size(1), x.size(1), dy.size(1))
+             .eligible;
+}
+
+// Gradient of conv2d(x, weight) for the [N, K, 1, 1] weight: (dy, x) -> dw
+at::Tensor py_conv1x1_wrw(const at::Tensor& dy, const at::Tensor& x,
+                          int64_t max_workgroups) {
+  TORCH_CHECK(max_workgroups >= 0, "conv1x1_wrw: max_workgroups >= 0");
+  TORCH_CHECK(py_conv1x1_wrw_eligible(dy, x),
+              "conv1x1_wrw: dy or x is not eligible");
+  const Conv1x1WrwPlan p =
+      conv1x1_wrw_plan(dy.numel() / dy.size(1), x.size(1), dy.size(1),
+                       clamp_workgroups(max_workgroups));
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dy.device().index());
+  // the layout the stock weight gradient has: channels_last, which for a
+  // 1x1 filter is the same dense [N, K] memory
+  auto dw = at::empty({p.n, p.k, 1, 1}, dy.options(),
+                      at::MemoryFormat::ChannelsLast);
+  auto part = at::empty({p.splits, p.n, p.k}, dy.options().dtype(at::kFloat));
+  launch_conv1x1_wrw(p, dy.data_ptr(), x.data_ptr(), part.data_ptr<float>(),
+                     dw.data_ptr(), bn_stream(dy));
+  return dw;
+}
+
+py::dict py_conv1x1_wrw_plan(int64_t rows, int64_t k, int64_t n,
+                             int64_t max_workgroups) {
+  const Conv1x1WrwPlan p =
+      conv1x1_wrw_plan(rows, k, n, clamp_workgroups(max_workgroups));
+  py::dict d;
+  d["eligible"] = p.eligible;
+  d["native"] = p.native;
+  d["threads"] = kConvThreads;
+  d["bn"] = p.bn;
+  d["bk"] = p.bk;
+  d["ntiles_n"] = p.ntiles_n;
+  d["ntiles_k"] = p.ntiles_k;
+  d["chunk_rows"] = p.chunk_rows;
+  d["row_chunks"] = p.row_chunks;
+  d["splits"] = p.splits;
+  d["grid"] = p.grid;
+  d["chunks_per_split"] = p.chunks_per_split;
+  d["lds_bytes"] = p.lds_bytes;
+  d["partial_floats"] = p.partial_floats;
+  return d;
+}
+
+// Test seam: the kernel's walk replayed on the host.  Entry [wg, i] holds
+// (n0, k0, split, row0, row1) of the i-th chunk of workgroup wg: the corner
+// of its tile of dW, the plane of the partials it writes and the rows it
+// sums; -1 once it has run out of chunks.
+at::Tensor py_conv1x1_wrw_walk(int64_t rows, int64_t k, int64_t n,
+                               int64_t max_workgroups) {
+  const Conv1x1WrwPlan p =
+      conv1x1_wrw_plan(rows, k, n, clamp_workgroups(max_workgroups));
+  TORCH_CHECK(p.eligible, "conv1x1_wrw_walk: shape is not eligible");
+  auto out = at::full({p.grid, p.chunks_per_split, 5}, -1,
+                      at::TensorOptions().dtype(at::kLong));
+  int64_t* o = out.data_ptr<int64_t>();
+  for (int wg = 0; wg < p.grid; wg++) {
+    const int tile = conv1x1_wrw_tile(p, wg), split = conv1x1_wrw_split(p, wg);
+    for (int i = 0; i < p.chunks_per_split; i++) {
+      const int ch = conv1x1_wrw_chunk(p, split, i);
+      if (ch >= p.row_chunks) break;
+      int64_t* e = o + ((int64_t)wg * p.chunks_per_split + i) * 5;
+      e[0] = (int64_t)(tile / p.ntiles_k) * p.bn;
+      e[1] = (int64_t)(tile % p.ntiles_k) * p.bk;
+      e[2] = split;
+      e[3] = (int64_t)ch * p.chunk_rows;
+      e[4] = std::min<int64_t>(e[3] + p.chunk_rows, p.rows);
+    }
+  }
+  return out;
+}
+
 void py_register_layer(int64_t bucket_idx, int64_t layer_idx, int64_t numel,
                        int64_t bits, int64_t bucket_size) {
   Registry::get().register_layer((int)bucket_idx, (int)layer_idx, numel,
@@ -1338,6 +1419,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("max_workgroups") = 0,
         "Test seam: conv1x1_walk for the plan of conv1x1_bwd_plan; channels "
         "are dx's.");
+  m.def("conv1x1_wrw", &cgx::py_conv1x1_wrw, py::arg("dy"), py::arg("x"),
+        py::arg("max_workgroups") = 0,
+        "Weight gradient of conv2d(x, weight) for a 1x1 / stride 1 convolution "
+        "on channels_last bf16 tensors: dw[n, k] = bf16(sum_r dy[r, n] * "
+        "x[r, k]) as [N, K, 1, 1], accumulated in fp32 in a fixed order and "
+        "rounded once.");
+  m.def("conv1x1_wrw_eligible", &cgx::py_conv1x1_wrw_eligible, py::arg("dy"),
+        py::arg("x"), "True where conv1x1_wrw takes (dy, x).");
+  m.def("conv1x1_wrw_plan", &cgx::py_conv1x1_wrw_plan, py::arg("rows"),
+        py::arg("k"), py::arg("n"), py::arg("max_workgroups") = 0,
+        "The launch geometry of conv1x1_wrw for dw [n, k] from dy [rows, n] "
+        "and x [rows, k], and `native`: whether the model uses it for this "
+        "problem.");
+  m.def("conv1x1_wrw_walk", &cgx::py_conv1x1_wrw_walk, py::arg("rows"),
+        py::arg("k"), py::arg("n"), py::arg("max_workgroups") = 0,
+        "Test seam: [grid, chunks_per_split, 5] int64, (n0, k0, split, row0, "
+        "row1) of every row chunk each workgroup visits (-1: none).");
   m.def("bn_act2_backward", &cgx::py_bn_act2_backward,
         "Backward of bn_act2_forward: (dy, x3, xd, mean3, invstd3, weight3, "
         "meand, invstdd, weightd, mask) -> (dx3, dxd, dgamma3, dbeta3, "

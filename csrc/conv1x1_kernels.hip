@@ -456,7 +456,234 @@ void launch_bwd_add(const Conv1x1Plan& p, const void* dy, const void* w,
   else launch_bwd_nt<8, ADD>(p, dy, w, skip, dx, stream);
 }
 
+// ---- backward-weights -------------------------------------------------------
+//
+// dW[N, K] = sum_r dY[r, n] * X[r, k] (plan: conv1x1_wrw_plan).  The contracted
+// index r is the slow one of both operands, so both MFMA operands are read
+// transposed.  A 64-row chunk of the tile's BN channels of dY and BK channels
+// of X is copied row by row into two LDS images; dY^T is the A operand and X
+// the B operand of v_mfma_f32_32x32x16_bf16, whose lane l wants channel l & 31
+// at the eight rows 8*(l >> 5) .. +7 of a 16-row step: two ds_read_b64_tr_b16,
+// each taking per 16-lane group a block of 4 rows x 16 channels.
+//
+// Image of a [64 rows][C channels] chunk: 64-byte cells (32 channels) in
+// 256-byte lines, cell u of row r at wrw_cell(r, u).  A transposed read of a
+// 32-lane half takes one cell (its two groups the cell's two 32-byte halves)
+// of the four rows 4m .. 4m+3, 8 bytes per lane: 256 bytes that must fall on
+// the 64 banks once.  Bank = (byte / 4) % 64, so the four cells must sit in
+// the four different 64-byte columns of a line:
+//   C >= 128  a row is C/128 whole lines, its cell u in column u & 3; the XOR
+//             with r & 3 moves the four rows to four different columns
+//   C == 64   a line holds rows 2v, 2v+1, cell u of row r in column
+//             2*(r & 1) + u; rows 4m, 4m+1 take columns {u, u+2} of their
+//             line, and the XOR with (r >> 1) & 1 moves rows 4m+2, 4m+3 to
+//             the other two
+// The 16-byte writes of the copy fill whole lines from consecutive lanes and
+// are conflict-free under any permutation of a line's cells.  Every address
+// is a multiple of 8 and inside the image, and no branch that diverges within
+// a wave encloses the reads: EXEC is all ones.
+//
+// The global loads of the next chunk are issued before the MFMAs of the
+// current one and wait in registers; rows past R are loaded from row R-1 and
+// replaced by zeros.  Each workgroup stores its fp32 tile to its split's
+// plane of `part`; conv1x1_wrw_finalize sums the planes in a fixed order.
+
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+
+template <int C>
+__device__ inline int wrw_cell(int r, int u) {
+  const int lin = r * (C / 32) + u;
+  const int swz = C == 64 ? (r >> 1) & 1 : r & 3;
+  return 256 * (lin >> 2) + 64 * ((lin & 3) ^ swz);
+}
+
+// The chunk's rows r0 .. r0+63 of channels c0 .. c0+C of src[R, width]: thread
+// tid's C/32 vectors.
+template <int C>
+__device__ inline void wrw_load(uint4 (&v)[C / 32], const uint4* __restrict__ src,
+                                int width, int c0, int64_t r0, int64_t rows,
+                                int tid) {
+#pragma unroll
+  for (int i = 0; i < C / 32; i++) {
+    const int idx = tid + i * kT, row = idx / (C / 8), q = idx % (C / 8);
+    const bool live = r0 + row < rows;
+    const int64_t r = live ? r0 + row : rows - 1;
+    const uint4 t = src[(r * width + c0) / 8 + q];
+    v[i] = live ? t : make_uint4(0, 0, 0, 0);
+  }
+}
+
+template <int C>
+__device__ inline void wrw_store(char* img, const uint4 (&v)[C / 32], int tid) {
+#pragma unroll
+  for (int i = 0; i < C / 32; i++) {
+    const int idx = tid + i * kT, row = idx / (C / 8), q = idx % (C / 8);
+    *reinterpret_cast<uint4*>(img + wrw_cell<C>(row, q >> 2) + 16 * (q & 3)) =
+        v[i];
+  }
+}
+
+// The operand of one 16-row step from a lane's base address: rows +0 .. +3 in
+// elements 0 .. 3, rows +4 .. +7 in elements 4 .. 7.
+template <int C>
+__device__ inline bf16x8 wrw_operand(char* img, int base, int s) {
+  char* a = img + base + s * 16 * 2 * C;
+  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+      (lds_bf16x4*)a);
+  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+      (lds_bf16x4*)(a + 4 * 2 * C));
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+template <int BN, int BK>
+__global__ __launch_bounds__(kT) void conv1x1_wrw(
+    const uint4* __restrict__ dy, const uint4* __restrict__ x,
+    float* __restrict__ part, Conv1x1WrwPlan p) {
+  extern __shared__ uint4 lds[];
+  constexpr int MT = BN / 64, KT = BK / 64;  // 32x32 tiles of a wave
+  char* img_n = reinterpret_cast<char*>(lds);
+  char* img_k = img_n + kWrwChunkRows * BN * 2;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int c = lane & 31, h = lane >> 5;
+  const int wn = wave >> 1, wk = wave & 1;
+  const int tile = conv1x1_wrw_tile(p, blockIdx.x);
+  const int split = conv1x1_wrw_split(p, blockIdx.x);
+  const int n0 = (tile / p.ntiles_k) * BN, k0 = (tile % p.ntiles_k) * BK;
+
+  // Lane 4q+pp of 16-lane group g supplies row q, channels 4pp .. 4pp+3 of the
+  // group's block: rows 8h+q of the step's first read, channels 16*(g & 1) ..
+  // of the cell.
+  const int q = (lane >> 2) & 3;
+  const int in_cell = 32 * ((lane >> 4) & 1) + 8 * (lane & 3);
+  int an[MT], ak[KT];
+#pragma unroll
+  for (int j = 0; j < MT; j++)
+    an[j] = wrw_cell<BN>(8 * h + q, wn * MT + j) + in_cell;
+#pragma unroll
+  for (int j = 0; j < KT; j++)
+    ak[j] = wrw_cell<BK>(8 * h + q, wk * KT + j) + in_cell;
+
+  f32x16 acc[MT][KT];
+#pragma unroll
+  for (int jm = 0; jm < MT; jm++)
+#pragma unroll
+    for (int jk = 0; jk < KT; jk++)
+#pragma unroll
+      for (int e = 0; e < 16; e++) acc[jm][jk][e] = 0.f;
+
+  uint4 vn[BN / 32], vk[BK / 32];
+  wrw_load<BN>(vn, dy, p.n, n0, (int64_t)split * kWrwChunkRows, p.rows, tid);
+  wrw_load<BK>(vk, x, p.k, k0, (int64_t)split * kWrwChunkRows, p.rows, tid);
+
+  for (int i = 0; i < p.chunks_per_split; i++) {
+    if (conv1x1_wrw_chunk(p, split, i) >= p.row_chunks) break;
+    __syncthreads();  // the previous chunk has been read
+    wrw_store<BN>(img_n, vn, tid);
+    wrw_store<BK>(img_k, vk, tid);
+    __syncthreads();
+    const int next = conv1x1_wrw_chunk(p, split, i + 1);
+    if (next < p.row_chunks) {
+      wrw_load<BN>(vn, dy, p.n, n0, (int64_t)next * kWrwChunkRows, p.rows, tid);
+      wrw_load<BK>(vk, x, p.k, k0, (int64_t)next * kWrwChunkRows, p.rows, tid);
+    }
+#pragma unroll
+    for (int s = 0; s < kWrwChunkRows / 16; s++) {
+      bf16x8 a[MT], b[KT];
+#pragma unroll
+      for (int j = 0; j < MT; j++) a[j] = wrw_operand<BN>(img_n, an[j], s);
+#pragma unroll
+      for (int j = 0; j < KT; j++) b[j] = wrw_operand<BK>(img_k, ak[j], s);
+#pragma unroll
+      for (int jm = 0; jm < MT; jm++)
+#pragma unroll
+        for (int jk = 0; jk < KT; jk++)
+          acc[jm][jk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              a[jm], b[jk], acc[jm][jk], 0, 0, 0);
+    }
+  }
+
+  // lane (c, h) holds dW[n][k] for k = its column c and 16 rows n
+  float* out = part + (int64_t)split * p.n * p.k;
+#pragma unroll
+  for (int jm = 0; jm < MT; jm++)
+#pragma unroll
+    for (int jk = 0; jk < KT; jk++)
+#pragma unroll
+      for (int e = 0; e < 16; e++) {
+        const int n = n0 + (wn * MT + jm) * 32 + acc_row(e, h);
+        const int k = k0 + (wk * KT + jk) * 32 + c;
+        out[(int64_t)n * p.k + k] = acc[jm][jk][e];
+      }
+}
+
+// dw[v] = bf16(part[0][v] + part[1][v] + ...) for the vectors v of eight
+// elements, each summed by a group of g lanes (a power of two up to 16): lane
+// j of the group adds the splits j*per .. (j+1)*per - 1 in index order, then
+// the g sums are added as a tree over the lanes.  The order is fixed: two
+// runs give the same bits.  A wave takes 64/g consecutive vectors and its
+// lane l the vector l % (64/g) of them as j = l / (64/g), so that the lanes
+// of one j read consecutive memory.  vecs * g is a multiple of the workgroup.
+__global__ __launch_bounds__(kT) void conv1x1_wrw_finalize(
+    const float4* __restrict__ part, uint4* __restrict__ dw, int splits,
+    int64_t vecs, int g) {
+  const int lane = threadIdx.x & 63, vw = 64 / g;
+  const int64_t wave = ((int64_t)blockIdx.x * kT + threadIdx.x) >> 6;
+  const int64_t v = wave * vw + lane % vw;
+  const int j = lane / vw, per = (splits + g - 1) / g;
+  const int s1 = (j + 1) * per < splits ? (j + 1) * per : splits;
+  float f[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int s = j * per; s < s1; s++) {
+    const float4 lo = part[(s * vecs + v) * 2];
+    const float4 hi = part[(s * vecs + v) * 2 + 1];
+    f[0] += lo.x, f[1] += lo.y, f[2] += lo.z, f[3] += lo.w;
+    f[4] += hi.x, f[5] += hi.y, f[6] += hi.z, f[7] += hi.w;
+  }
+  for (int off = 32; off >= vw; off >>= 1)
+#pragma unroll
+    for (int e = 0; e < 8; e++) f[e] += __shfl_down(f[e], off);
+  if (j == 0)
+    dw[v] = make_uint4(pack_bf16(f[0], f[1]), pack_bf16(f[2], f[3]),
+                       pack_bf16(f[4], f[5]), pack_bf16(f[6], f[7]));
+}
+
+template <int BN, int BK>
+void launch_wrw(const Conv1x1WrwPlan& p, const void* dy, const void* x,
+                float* part, hipStream_t stream) {
+  hipLaunchKernelGGL((conv1x1_wrw<BN, BK>), dim3(p.grid), dim3(kT),
+                     p.lds_bytes, stream, static_cast<const uint4*>(dy),
+                     static_cast<const uint4*>(x), part, p);
+}
+
+template <int BN>
+void launch_wrw_bn(const Conv1x1WrwPlan& p, const void* dy, const void* x,
+                   float* part, hipStream_t stream) {
+  if (p.bk == 64) launch_wrw<BN, 64>(p, dy, x, part, stream);
+  else if (p.bk == 128) launch_wrw<BN, 128>(p, dy, x, part, stream);
+  else if constexpr (BN < 256) launch_wrw<BN, 256>(p, dy, x, part, stream);
+  else TORCH_CHECK(false, "conv1x1_wrw: no 256 x 256 tile");
+}
+
 }  // namespace
+
+void launch_conv1x1_wrw(const Conv1x1WrwPlan& p, const void* dy, const void* x,
+                        float* part, void* dw, hipStream_t stream) {
+  TORCH_CHECK(p.eligible, "conv1x1_wrw: shape is not eligible");
+  if (p.bn == 64) launch_wrw_bn<64>(p, dy, x, part, stream);
+  else if (p.bn == 128) launch_wrw_bn<128>(p, dy, x, part, stream);
+  else launch_wrw_bn<256>(p, dy, x, part, stream);
+  CGX_HIP_CHECK(hipGetLastError());
+  // lanes per vector: as many as the splits give work to, until the grid
+  // has four waves for every SIMD
+  const int64_t vecs = (int64_t)p.n * p.k / 8;
+  int g = 1;
+  while (g < 16 && 2 * g <= p.splits && vecs * g < 4 * kConvCus * kT) g *= 2;
+  hipLaunchKernelGGL(conv1x1_wrw_finalize, dim3((unsigned)(vecs * g / kT)),
+                     dim3(kT), 0, stream,
+                     reinterpret_cast<const float4*>(part),
+                     static_cast<uint4*>(dw), p.splits, vecs, g);
+  CGX_HIP_CHECK(hipGetLastError());
+}
 
 void launch_conv1x1_bwd_data(const Conv1x1Plan& p, const void* dy,
                              const void* w, const void* skip, void* dx,

@@ -86,7 +86,71 @@ void set_grid(Conv1x1Plan& p, int64_t splits, int max_workgroups) {
   p.tiles_per_split = (p.row_tiles + p.splits - 1) / p.splits;
 }
 
+// The backward-weights problems (K, N, rows) at which conv1x1_wrw plus its
+// finalize met the same rule against MIOpen's workspace fill, igemm_wrw and
+// cast (benchmarks/RESULTS.md): eleven of ResNet-50's twelve at batch 256.
+// At 64->64 the ranges of the two overlap, and it stays stock.
+constexpr Measured kNativeWrw[] = {
+    {64, 256, 802816},  {256, 64, 802816},  {256, 128, 802816},
+    {128, 512, 200704}, {512, 128, 200704}, {512, 256, 200704},
+    {256, 1024, 50176}, {1024, 256, 50176}, {1024, 512, 50176},
+    {512, 2048, 12544}, {2048, 512, 12544},
+};
+
+bool measured_faster_wrw(int64_t rows, int k, int n) {
+  for (const Measured& m : kNativeWrw)
+    if (m.k == k && m.n == n && m.rows == rows) return true;
+  return false;
+}
+
 }  // namespace
+
+Conv1x1WrwPlan conv1x1_wrw_plan(int64_t rows, int64_t k, int64_t n,
+                                int max_workgroups) {
+  Conv1x1WrwPlan p;
+  p.rows = rows;
+  p.eligible = pow2_in(k, 64, 2048) && pow2_in(n, 64, 2048) && rows >= 2 &&
+               rows <= kBnMaxRows;
+  if (!p.eligible) return p;
+  p.k = (int)k;
+  p.n = (int)n;
+  p.native = measured_faster_wrw(rows, p.k, p.n);
+  p.chunk_rows = kWrwChunkRows;
+  p.row_chunks = (int)((rows + kWrwChunkRows - 1) / kWrwChunkRows);
+  // No more splits than keep the partials, 4*N*K bytes per split written and
+  // read back once, within half of the 2*R*(N+K) bytes of the inputs.
+  const int64_t cap = std::min<int64_t>(
+      p.row_chunks, std::max<int64_t>(1, rows * (n + k) / (8 * n * k)));
+  // The widest tile, which reads the inputs the fewest times; 256 x 256 would
+  // leave one wave per SIMD.  Where the cap on the splits, not the rows, keeps
+  // the grid below one workgroup per CU, more and smaller tiles fill it.
+  p.bn = (int)std::min<int64_t>(n, 256);
+  p.bk = (int)std::min<int64_t>(k, 256);
+  if (p.bn == 256 && p.bk == 256) p.bn = 128;
+  while (cap < p.row_chunks && std::max(p.bn, p.bk) > 128 &&
+         (n / p.bn) * (k / p.bk) * cap < kConvCus)
+    (p.bn >= p.bk ? p.bn : p.bk) /= 2;
+  p.ntiles_n = p.n / p.bn;
+  p.ntiles_k = p.k / p.bk;
+  p.lds_bytes = kWrwChunkRows * (p.bn + p.bk) * 2;
+  // four waves per SIMD with one 32x32 accumulator tile per wave, three with
+  // two, two with four, one with eight
+  const int acc_tiles = (p.bn / 64) * (p.bk / 64);
+  const int by_regs =
+      acc_tiles == 1 ? 4 : acc_tiles == 2 ? 3 : acc_tiles == 4 ? 2 : 1;
+  const int per_cu = std::min(kConvLdsBytes / p.lds_bytes, by_regs);
+  const int tiles = p.ntiles_n * p.ntiles_k;
+  int64_t splits =
+      std::min<int64_t>(cap, std::max(1, kConvCus * per_cu / tiles));
+  if (splits > 8) splits -= splits % 8;  // conv1x1_wrw_split
+  if (max_workgroups > 0)
+    splits = std::min<int64_t>(splits, std::max(1, max_workgroups / tiles));
+  p.splits = (int)splits;
+  p.grid = tiles * p.splits;
+  p.chunks_per_split = (p.row_chunks + p.splits - 1) / p.splits;
+  p.partial_floats = (int64_t)p.splits * p.n * p.k;
+  return p;
+}
 
 Conv1x1Plan conv1x1_plan(int64_t rows, int64_t k, int64_t n,
                          int max_workgroups) {

@@ -101,6 +101,66 @@ inline BnPartials conv1x1_partials(const float* part, int n, int splits,
   return q;
 }
 
+// Backward-weights of the same convolution, dW[N, K] = dY[R, N]^T * X[R, K]
+// (conv1x1_wrw in conv1x1_kernels.hip).  The contracted index R is the slow
+// one of both operands.  A workgroup owns a bn x bk tile of dW (its four waves
+// 2 x 2, each bn/2 x bk/2) and one of `splits` slices of the rows: it walks
+// 64-row chunks split, split + splits, ... of dY's and X's channels of the
+// tile, and writes its fp32 tile to part[split][N][K].  conv1x1_wrw_finalize
+// sums the splits of an element in a fixed order and rounds once to bf16: no
+// atomics, the same bits every run.
+constexpr int kWrwChunkRows = 64;
+
+struct Conv1x1WrwPlan {
+  int64_t rows = 0;  // R
+  int k = 0, n = 0;
+  bool eligible = false;
+  bool native = false;  // measured faster than MIOpen's fill + igemm + cast
+  int bn = 0, bk = 0;   // the workgroup's tile of dW
+  int ntiles_n = 0, ntiles_k = 0;
+  int chunk_rows = 0;
+  int row_chunks = 0;  // ceil(R / chunk_rows)
+  int splits = 0;      // workgroups per channel tile
+  int grid = 0;        // ntiles_n * ntiles_k * splits
+  int chunks_per_split = 0;  // longest walk
+  int lds_bytes = 0;
+  int64_t partial_floats = 0;  // splits * N * K
+};
+
+// K and N powers of two in [64, 2048], 2 <= R <= kBnMaxRows, as the other two.
+// `max_workgroups` > 0 caps the grid.
+Conv1x1WrwPlan conv1x1_wrw_plan(int64_t rows, int64_t k, int64_t n,
+                                int max_workgroups = 0);
+
+// Workgroup `wg` owns channel tile conv1x1_wrw_tile (tile t covers rows
+// (t / ntiles_k) * bn of dW and columns (t % ntiles_k) * bk) and row slice
+// conv1x1_wrw_split.  The workgroups of one slice read the same rows, so they
+// are given block indices 8 apart, which land on one XCD and share its L2,
+// wherever the splits divide by 8; this is for speed only.
+__host__ __device__ inline int conv1x1_wrw_tiles(const Conv1x1WrwPlan& p) {
+  return p.ntiles_n * p.ntiles_k;
+}
+__host__ __device__ inline int conv1x1_wrw_tile(const Conv1x1WrwPlan& p,
+                                                int wg) {
+  const int tiles = conv1x1_wrw_tiles(p);
+  return p.splits % 8 == 0 ? (wg / 8) % tiles : wg % tiles;
+}
+__host__ __device__ inline int conv1x1_wrw_split(const Conv1x1WrwPlan& p,
+                                                 int wg) {
+  const int tiles = conv1x1_wrw_tiles(p);
+  return p.splits % 8 == 0 ? (wg / 8 / tiles) * 8 + wg % 8 : wg / tiles;
+}
+// the i-th row chunk of a split; the walk ends at the first one >= row_chunks
+__host__ __device__ inline int conv1x1_wrw_chunk(const Conv1x1WrwPlan& p,
+                                                 int split, int i) {
+  return split + i * p.splits;
+}
+
+// dw[N, K] bf16 from dy[R, N] and x[R, K] bf16 through part[splits, N, K]
+// fp32, which needs no initialisation; every pointer 16-byte aligned.
+void launch_conv1x1_wrw(const Conv1x1WrwPlan& p, const void* dy, const void* x,
+                        float* part, void* dw, hipStream_t stream);
+
 // y[R, N] bf16 and part[splits, pstride] fp32 from x[R, K] and w[N, K] bf16;
 // every pointer 16-byte aligned.
 void launch_conv1x1_stats(const Conv1x1Plan& p, const void* x, const void* w,

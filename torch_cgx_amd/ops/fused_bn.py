@@ -35,9 +35,16 @@ in the plan has measured it faster than the stock backward-data.
 ``conv_bn_act_fork`` is ``conv_bn_act`` at the input of a residual block: it
 also returns the tensor the skip path continues from, and the gradient
 arriving over that path is then added in the GEMM's epilogue, not by
-autograd in a pass of its own.  The weight gradient stays the stock one.
+autograd in a pass of its own.
 ``CGX_NATIVE_CONV1X1_BWD=0|1|all`` works like the forward switch and is off
 wherever that one is.
+
+The weight gradient is the third GEMM, ``dW = dY^T X`` with the rows
+contracted (``_C.conv1x1_wrw``): a split over the rows whose fp32 partials a
+second kernel sums in a fixed order, so it gives the same bits every run.  It
+too is taken where its own table has measured it faster than the stock
+weight gradient; ``CGX_NATIVE_CONV1X1_WRW=0|1|all`` is its switch, off
+wherever the forward switch is.
 
 ``CGX_FUSED_BN=0`` switches all native paths off.
 """
@@ -168,7 +175,8 @@ def bn_act(bn: torch.nn.BatchNorm2d, x: torch.Tensor,
 
 class _Conv1x1Stats(torch.autograd.Function):
     """The 1x1 convolution and the BatchNorm partials of its output; the
-    backward is the stock convolution backward on the same operands."""
+    backward is the stock convolution backward on the same operands, but for
+    the weight gradient where the native one is taken."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
@@ -182,9 +190,14 @@ class _Conv1x1Stats(torch.autograd.Function):
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, dy, _dpart):
         x, weight = ctx.saved_tensors
-        dx, dw, _ = torch.ops.aten.convolution_backward(
-            dy, x, weight, None, (1, 1), (0, 0), (1, 1), False, (0, 0), 1,
-            (ctx.needs_input_grad[0], ctx.needs_input_grad[1], False))
+        need_dx, need_dw = ctx.needs_input_grad[:2]
+        if need_dw and _conv1x1_dw_native(dy, x):
+            dw = _conv1x1_dw(dy, x, weight)
+            dx = None
+            if need_dx:
+                dx = _conv1x1_backward(dy, x, weight, (True, False, False))[0]
+            return dx, dw
+        dx, dw, _ = _conv1x1_backward(dy, x, weight, (need_dx, need_dw, False))
         return dx, dw
 
 
@@ -194,7 +207,7 @@ class _Conv1x1Fork(torch.autograd.Function):
     ``fork`` its input once more as ``skip``, for the residual path to go on
     from.  The backward then receives the gradients of both at once, and the
     native backward-data GEMM adds the skip gradient in its epilogue instead
-    of autograd in a pass of its own.  The weight gradient is the stock one."""
+    of autograd in a pass of its own."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
@@ -215,7 +228,7 @@ class _Conv1x1Fork(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         dx = dw = None
         if dy is not None and ctx.needs_input_grad[1]:
-            dw = _conv1x1_backward(dy, x, weight, (False, True, False))[1]
+            dw = _conv1x1_dw(dy, x, weight)
         if ctx.needs_input_grad[0]:
             dx = dskip if dy is None else _conv1x1_dx(dy, x, weight, dskip)
         return dx, dw, None, None
@@ -224,6 +237,23 @@ class _Conv1x1Fork(torch.autograd.Function):
 def _conv1x1_backward(dy, x, weight, mask):
     return torch.ops.aten.convolution_backward(
         dy, x, weight, None, (1, 1), (0, 0), (1, 1), False, (0, 0), 1, mask)
+
+
+def _conv1x1_dw_native(dy, x) -> bool:
+    mode = native_conv1x1_wrw_mode()
+    if mode == "0" or not _C.conv1x1_wrw_eligible(dy, x):
+        return False
+    plan = _C.conv1x1_wrw_plan(x.numel() // x.shape[1], x.shape[1],
+                               dy.shape[1])
+    return plan["native"] or mode == "all"
+
+
+def _conv1x1_dw(dy, x, weight):
+    """The weight gradient: the native GEMM where the plan has measured it
+    faster, else the stock one."""
+    if _conv1x1_dw_native(dy, x):
+        return _C.conv1x1_wrw(dy, x)
+    return _conv1x1_backward(dy, x, weight, (False, True, False))[1]
 
 
 def _conv1x1_dx(dy, x, weight, dskip):
@@ -252,6 +282,14 @@ def native_conv1x1_bwd_mode() -> str:
     if native_conv1x1_mode() == "0":
         return "0"
     return os.environ.get("CGX_NATIVE_CONV1X1_BWD", "1")
+
+
+def native_conv1x1_wrw_mode() -> str:
+    """As native_conv1x1_mode, for the backward-weights GEMM; off wherever
+    the forward switch is."""
+    if native_conv1x1_mode() == "0":
+        return "0"
+    return os.environ.get("CGX_NATIVE_CONV1X1_WRW", "1")
 
 
 def _conv1x1_shape(conv, bn, x):
@@ -298,6 +336,14 @@ def _conv1x1_bwd_native(shape, with_add) -> bool:
     return plan["eligible"] and (plan["native"] or mode == "all")
 
 
+def _conv1x1_wrw_native(shape) -> bool:
+    mode = native_conv1x1_wrw_mode()
+    if mode == "0":
+        return False
+    plan = _C.conv1x1_wrw_plan(*shape)
+    return plan["eligible"] and (plan["native"] or mode == "all")
+
+
 def _conv(conv, bn, x, fork=False):
     """``(conv(x), part, skip)``: ``part`` are the partials for ``bn``, or
     None where the stock convolution ran; ``skip`` is what a residual path
@@ -309,7 +355,8 @@ def _conv(conv, bn, x, fork=False):
     fwd = _conv1x1_native(shape)
     if torch.is_grad_enabled():
         fork = fork and _conv1x1_bwd_native(shape, True)
-        if fork or _conv1x1_bwd_native(shape, False):
+        if (fork or _conv1x1_bwd_native(shape, False)
+                or _conv1x1_wrw_native(shape)):
             y, part, skip = _Conv1x1Fork.apply(x, conv.weight, fwd, fork)
             return y, part, (skip if fork else x)
     if fwd:
