@@ -947,22 +947,24 @@ std::vector<int64_t> py_bn_partial_offsets(int64_t rows, int64_t channels,
 
 // ---- 1x1 convolution with statistics (conv1x1_plan.h) ----------------------
 
-Conv1x1Plan conv1x1_plan_of(const at::Tensor& x, const at::Tensor& weight,
-                            int64_t max_workgroups) {
-  return conv1x1_plan(x.numel() / x.size(1), x.size(1), weight.size(0),
-                      (int)std::min<int64_t>(max_workgroups, 1 << 20));
+// R of a channels_last activation
+int64_t rows_of(const at::Tensor& t) { return t.numel() / t.size(1); }
+
+// A dense, 16-byte aligned bf16 [N, K, 1, 1] weight on the device of `like`.
+bool conv_weight_ok(const at::Tensor& weight, const at::Tensor& like) {
+  return weight.is_cuda() && weight.device() == like.device() &&
+         weight.scalar_type() == at::kBFloat16 && weight.dim() == 4 &&
+         weight.size(2) == 1 && weight.size(3) == 1 &&
+         weight.is_contiguous() &&
+         reinterpret_cast<uintptr_t>(weight.data_ptr()) % 16 == 0;
 }
 
 // What the kernel takes: a bf16 channels_last activation as for the BatchNorm
-// kernels and a dense bf16 [N, K, 1, 1] weight on the same device.
+// kernels and the convolution's weight, K wide.
 bool py_conv1x1_eligible(const at::Tensor& x, const at::Tensor& weight) {
-  return bn_tensor_ok(x) && weight.is_cuda() &&
-         weight.device() == x.device() &&
-         weight.scalar_type() == at::kBFloat16 && weight.dim() == 4 &&
-         weight.size(1) == x.size(1) && weight.size(2) == 1 &&
-         weight.size(3) == 1 && weight.is_contiguous() &&
-         reinterpret_cast<uintptr_t>(weight.data_ptr()) % 16 == 0 &&
-         conv1x1_plan_of(x, weight, 0).eligible;
+  return bn_tensor_ok(x) && conv_weight_ok(weight, x) &&
+         weight.size(1) == x.size(1) &&
+         conv1x1_plan(rows_of(x), x.size(1), weight.size(0)).eligible;
 }
 
 // conv2d(x, weight) for a 1x1 / stride 1 convolution -> (y, part); part holds
@@ -973,7 +975,8 @@ std::tuple<at::Tensor, at::Tensor> py_conv1x1_stats(const at::Tensor& x,
   TORCH_CHECK(max_workgroups >= 0, "conv1x1_stats: max_workgroups >= 0");
   TORCH_CHECK(py_conv1x1_eligible(x, weight),
               "conv1x1_stats: input or weight is not eligible");
-  const Conv1x1Plan p = conv1x1_plan_of(x, weight, max_workgroups);
+  const Conv1x1Plan p =
+      conv1x1_plan(rows_of(x), x.size(1), weight.size(0), max_workgroups);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device().index());
   auto y = at::empty({x.size(0), p.n, x.size(2), x.size(3)}, x.options(),
                      at::MemoryFormat::ChannelsLast);
@@ -983,9 +986,9 @@ std::tuple<at::Tensor, at::Tensor> py_conv1x1_stats(const at::Tensor& x,
   return {y, part};
 }
 
-py::dict py_conv1x1_plan(int64_t rows, int64_t k, int64_t n,
-                         int64_t max_workgroups) {
-  const Conv1x1Plan p = conv1x1_plan(rows, k, n, (int)max_workgroups);
+// The keys the forward's and the backward-data plan share.  For the backward
+// tile_channels / ntiles are over dX's K channels, k_chunk(s) over dY's N.
+py::dict conv1x1_plan_dict(const Conv1x1Plan& p) {
   py::dict d;
   d["eligible"] = p.eligible;
   d["native"] = p.native;
@@ -1001,8 +1004,15 @@ py::dict py_conv1x1_plan(int64_t rows, int64_t k, int64_t n,
   d["splits"] = p.splits;
   d["grid"] = p.grid;
   d["tiles_per_split"] = p.tiles_per_split;
-  d["run"] = p.run;
   d["lds_bytes"] = p.lds_bytes;
+  return d;
+}
+
+py::dict py_conv1x1_plan(int64_t rows, int64_t k, int64_t n,
+                         int64_t max_workgroups) {
+  const Conv1x1Plan p = conv1x1_plan(rows, k, n, max_workgroups);
+  py::dict d = conv1x1_plan_dict(p);
+  d["run"] = p.run;
   d["partial_stride"] = p.pstride;
   d["partial_floats"] = p.partial_floats;
   return d;
@@ -1032,29 +1042,21 @@ at::Tensor conv1x1_walk_of(const Conv1x1Plan& p) {
 
 at::Tensor py_conv1x1_walk(int64_t rows, int64_t k, int64_t n,
                            int64_t max_workgroups) {
-  const Conv1x1Plan p = conv1x1_plan(rows, k, n, (int)max_workgroups);
+  const Conv1x1Plan p = conv1x1_plan(rows, k, n, max_workgroups);
   TORCH_CHECK(p.eligible, "conv1x1_walk: shape is not eligible");
   return conv1x1_walk_of(p);
 }
 
 // ---- 1x1 convolution backward-data with the skip gradient added ------------
 
-int clamp_workgroups(int64_t max_workgroups) {
-  return (int)std::min<int64_t>(max_workgroups, 1 << 20);
-}
-
 // dy as the BatchNorm kernels take it, the convolution's dense bf16
 // [N, K, 1, 1] weight, and a skip gradient, if any, of dX's shape and layout.
 bool py_conv1x1_bwd_eligible(const at::Tensor& dy, const at::Tensor& weight,
                              const c10::optional<at::Tensor>& skip) {
-  if (!(bn_tensor_ok(dy) && weight.is_cuda() &&
-        weight.device() == dy.device() &&
-        weight.scalar_type() == at::kBFloat16 && weight.dim() == 4 &&
-        weight.size(0) == dy.size(1) && weight.size(2) == 1 &&
-        weight.size(3) == 1 && weight.is_contiguous() &&
-        reinterpret_cast<uintptr_t>(weight.data_ptr()) % 16 == 0 &&
-        conv1x1_bwd_plan(dy.numel() / dy.size(1), weight.size(1),
-                         weight.size(0), skip.has_value())
+  if (!(bn_tensor_ok(dy) && conv_weight_ok(weight, dy) &&
+        weight.size(0) == dy.size(1) &&
+        conv1x1_bwd_plan(rows_of(dy), weight.size(1), weight.size(0),
+                         skip.has_value())
             .eligible))
     return false;
   if (!skip.has_value()) return true;
@@ -1072,9 +1074,9 @@ at::Tensor py_conv1x1_bwd_data(const at::Tensor& dy, const at::Tensor& weight,
   TORCH_CHECK(max_workgroups >= 0, "conv1x1_bwd_data: max_workgroups >= 0");
   TORCH_CHECK(py_conv1x1_bwd_eligible(dy, weight, skip),
               "conv1x1_bwd_data: dy, weight or skip is not eligible");
-  const Conv1x1Plan p = conv1x1_bwd_plan(
-      dy.numel() / dy.size(1), weight.size(1), weight.size(0),
-      skip.has_value(), clamp_workgroups(max_workgroups));
+  const Conv1x1Plan p =
+      conv1x1_bwd_plan(rows_of(dy), weight.size(1), weight.size(0),
+                       skip.has_value(), max_workgroups);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(dy.device().index());
   auto dx = at::empty({dy.size(0), p.n, dy.size(2), dy.size(3)}, dy.options(),
                       at::MemoryFormat::ChannelsLast);
@@ -1084,35 +1086,16 @@ at::Tensor py_conv1x1_bwd_data(const at::Tensor& dy, const at::Tensor& weight,
   return dx;
 }
 
-// The keys of conv1x1_plan that the backward has, with the same meaning:
-// tile_channels / ntiles are over dX's K channels, k_chunk(s) over dY's N.
 py::dict py_conv1x1_bwd_plan(int64_t rows, int64_t k, int64_t n, bool with_add,
                              int64_t max_workgroups) {
-  const Conv1x1Plan p =
-      conv1x1_bwd_plan(rows, k, n, with_add, clamp_workgroups(max_workgroups));
-  py::dict d;
-  d["eligible"] = p.eligible;
-  d["native"] = p.native;
-  d["threads"] = kConvThreads;
-  d["tile_rows"] = kConvTileRows;
-  d["mfma_tiles"] = p.nt;
-  d["tile_channels"] = p.bn;
-  d["ntiles"] = p.ntiles;
-  d["k_chunk"] = p.kc;
-  d["k_chunks"] = p.nchunks;
-  d["resident"] = p.resident;
-  d["row_tiles"] = p.row_tiles;
-  d["splits"] = p.splits;
-  d["grid"] = p.grid;
-  d["tiles_per_split"] = p.tiles_per_split;
-  d["lds_bytes"] = p.lds_bytes;
-  return d;
+  return conv1x1_plan_dict(
+      conv1x1_bwd_plan(rows, k, n, with_add, max_workgroups));
 }
 
 at::Tensor py_conv1x1_bwd_walk(int64_t rows, int64_t k, int64_t n,
                                bool with_add, int64_t max_workgroups) {
   const Conv1x1Plan p =
-      conv1x1_bwd_plan(rows, k, n, with_add, clamp_workgroups(max_workgroups));
+      conv1x1_bwd_plan(rows, k, n, with_add, max_workgroups);
   TORCH_CHECK(p.eligible, "conv1x1_bwd_walk: shape is not eligible");
   return conv1x1_walk_of(p);
 }
@@ -1124,8 +1107,7 @@ bool py_conv1x1_wrw_eligible(const at::Tensor& dy, const at::Tensor& x) {
   return bn_tensor_ok(dy) && bn_tensor_ok(x) && x.device() == dy.device() &&
          x.size(0) == dy.size(0) && x.size(2) == dy.size(2) &&
          x.size(3) == dy.size(3) &&
-         conv1x1_wrw_plan(dy.numel() / dy.size(1), x.size(1), dy.size(1))
-             .eligible;
+         conv1x1_wrw_plan(rows_of(dy), x.size(1), dy.size(1)).eligible;
 }
 
 // Gradient of conv2d(x, weight) for the [N, K, 1, 1] weight: (dy, x) -> dw
@@ -1135,8 +1117,7 @@ at::Tensor py_conv1x1_wrw(const at::Tensor& dy, const at::Tensor& x,
   TORCH_CHECK(py_conv1x1_wrw_eligible(dy, x),
               "conv1x1_wrw: dy or x is not eligible");
   const Conv1x1WrwPlan p =
-      conv1x1_wrw_plan(dy.numel() / dy.size(1), x.size(1), dy.size(1),
-                       clamp_workgroups(max_workgroups));
+      conv1x1_wrw_plan(rows_of(dy), x.size(1), dy.size(1), max_workgroups);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(dy.device().index());
   // the layout the stock weight gradient has: channels_last, which for a
   // 1x1 filter is the same dense [N, K] memory
@@ -1150,8 +1131,7 @@ at::Tensor py_conv1x1_wrw(const at::Tensor& dy, const at::Tensor& x,
 
 py::dict py_conv1x1_wrw_plan(int64_t rows, int64_t k, int64_t n,
                              int64_t max_workgroups) {
-  const Conv1x1WrwPlan p =
-      conv1x1_wrw_plan(rows, k, n, clamp_workgroups(max_workgroups));
+  const Conv1x1WrwPlan p = conv1x1_wrw_plan(rows, k, n, max_workgroups);
   py::dict d;
   d["eligible"] = p.eligible;
   d["native"] = p.native;
@@ -1176,8 +1156,7 @@ py::dict py_conv1x1_wrw_plan(int64_t rows, int64_t k, int64_t n,
 // sums; -1 once it has run out of chunks.
 at::Tensor py_conv1x1_wrw_walk(int64_t rows, int64_t k, int64_t n,
                                int64_t max_workgroups) {
-  const Conv1x1WrwPlan p =
-      conv1x1_wrw_plan(rows, k, n, clamp_workgroups(max_workgroups));
+  const Conv1x1WrwPlan p = conv1x1_wrw_plan(rows, k, n, max_workgroups);
   TORCH_CHECK(p.eligible, "conv1x1_wrw_walk: shape is not eligible");
   auto out = at::full({p.grid, p.chunks_per_split, 5}, -1,
                       at::TensorOptions().dtype(at::kLong));

@@ -1,28 +1,32 @@
-// Forward of a 1x1 / stride 1 convolution on a channels_last bf16 activation,
-// Y[R, N] = X[R, K] * W[N, K]^T, that also leaves the per-channel
-// (count, mean, M2) partials of Y for the BatchNorm that follows: the output is
-// written once and never read back for its statistics.  Geometry:
-// conv1x1_plan.h.
+// The three GEMMs of a 1x1 / stride 1 convolution on channels_last bf16
+// activations.  Geometry: conv1x1_plan.h.
 //
-//   W   the workgroup's [bn, K] tile is copied to LDS once (or one [bn, kc]
+// Forward and backward-data are one persistent walk, gemm_walk, of
+// C[R, n] = A[R, k] * B[n, k]^T with two epilogues:
+//
+//   B   the workgroup's [bn, k] tile is copied to LDS once (or one [bn, kc]
 //       chunk per step where it does not fit), rows XOR-swizzled so that the
 //       ds_read_b128 of a B operand is conflict-free
-//   X   each lane loads the 16 bytes of its A operand (row lane&31, k
-//       8*(lane>>5) .. +7 of a 16-deep step) straight from global memory, one K
+//   A   each lane loads the 16 bytes of its A operand (row lane&31, k
+//       8*(lane>>5) .. +7 of a 16-deep step) straight from global memory, one
 //       chunk ahead of the MFMAs that use it
-//   Y   v_mfma_f32_32x32x16_bf16 leaves channel lane&31 of 16 rows in a lane.
-//       The accumulators are rounded to bf16 (as bf16_bits does), the rounded
-//       values go into the lane's running moments, and the tile is turned
-//       into 16-byte row vectors through a per-wave LDS strip of
-//       [32 rows][64 channels] and stored.
+//   C   v_mfma_f32_32x32x16_bf16 leaves channel lane&31 of 16 rows in a lane;
+//       the epilogue turns the tile into 16-byte row vectors through a
+//       per-wave LDS strip of [32 rows][64 channels] and stores them
 //
-// A lane keeps its moments across all tiles of its workgroup; at the end the
-// eight runs of a channel (4 waves x 2 lane halves) merge as a tree in a fixed
-// order.  No atomics: two runs give the same bits.
-//
-// The backward-data GEMM of the same convolution, which can add a second
-// tensor in its epilogue, follows the forward below.
+// conv1x1_stats is Y = X * W^T: its epilogue rounds the accumulators to bf16
+// (as bf16_bits does) and the rounded values go into the lane's running
+// moments, so that the output is never read back for the statistics of the
+// BatchNorm that follows.  A lane keeps its moments across all tiles of its
+// workgroup; at the end the eight runs of a channel (4 waves x 2 lane halves)
+// merge as a tree in a fixed order.  conv1x1_bwd_data is dX = dY * W with W^T
+// as B, transposed on the way into LDS; its epilogue can add a second tensor
+// before the one rounding.  conv1x1_wrw, the weight gradient, contracts the
+// rows and is an algorithm of its own.  No atomics anywhere: two runs give the
+// same bits.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "bn_moments.h"
 #include "check.h"
@@ -68,25 +72,41 @@ __device__ inline void stage_w(uint4* dst, const uint4* __restrict__ w, int n0,
   }
 }
 
-template <int NT, int KC, bool RES>
-__global__ __launch_bounds__(kT) void conv1x1_stats(
-    const uint4* __restrict__ x, const uint4* __restrict__ w,
-    uint4* __restrict__ y, float* __restrict__ part, Conv1x1Plan p) {
-  extern __shared__ uint4 lds[];
-  constexpr int BN = 32 * NT, cpr = KC / 8, steps = KC / 16;
-  constexpr int wchunks = BN * cpr;  // 16-byte chunks of one K chunk of W
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int c = lane & 31, h = lane >> 5;
-  const int ntile = conv1x1_ntile(p, blockIdx.x);
-  const int split = conv1x1_split(p, blockIdx.x);
-  const int n0 = ntile * BN;
-  const int kvec = p.k / 8, nvec = p.n / 8;
-  uint4* stage = lds + (RES ? p.nchunks : 1) * wchunks + wave * 256;
-  unsigned* stage32 = reinterpret_cast<unsigned*>(stage);
+// Vector u of the four that `lane` takes of the 256 16-byte vectors of a
+// wave's [32 rows][64 channels] bf16 strip: vector q of the strip's `row`,
+// which is vector g of a [R][8*nvec] tensor whose row r0 is the strip's first
+// and whose vector cv its leftmost.
+struct StripVec {
+  int row, q;
+  int64_t g;
+};
+__device__ inline StripVec strip_vec(int u, int lane, int64_t r0, int nvec,
+                                     int cv) {
+  const int idx = u * 64 + lane, row = idx >> 3, q = idx & 7;
+  return {row, q, (r0 + row) * nvec + cv + q};
+}
+
+// The walk of a workgroup over the row tiles of its split, for the channels
+// n0 .. n0 + 32*NT of C.  kStageB(dst, w, n0, width, kc, tid), stage_w or
+// stage_wt, copies chunk kc of the workgroup's B tile from the weight `w`,
+// `width` elements a row, to LDS at dst.  tile_done(t, r0, live, acc) takes
+// the accumulators of row tile t: of the wave's 32 rows from r0 on, the first
+// `live` exist.  tid and the wave, column c = lane & 31 and half h = lane >> 5
+// it gives are the kernel's own values: defined once, they compile as if the
+// walk were written out in the kernel.
+template <int NT, int KC, bool RES, auto kStageB, typename TileDone>
+__device__ __forceinline__ void gemm_walk(const uint4* am, const uint4* w,
+                                          int width, int n0, uint4* lds,
+                                          const Conv1x1Plan& p, int split,
+                                          int tid, int wave, int c, int h,
+                                          TileDone tile_done) {
+  constexpr int cpr = KC / 8, steps = KC / 16;
+  constexpr int wchunks = 32 * NT * cpr;  // 16-byte chunks of one chunk of B
+  const int kvec = p.k / 8;
 
   if (RES) {
     for (int kc = 0; kc < p.nchunks; kc++)
-      stage_w<NT, KC>(lds + kc * wchunks, w, n0, p.k, kc, tid);
+      kStageB(lds + kc * wchunks, w, n0, width, kc, tid);
     __syncthreads();
   }
 
@@ -94,10 +114,9 @@ __global__ __launch_bounds__(kT) void conv1x1_stats(
   auto a_row = [&](int t) {
     int64_t r = (int64_t)t * kConvTileRows + wave * 32 + c;
     r = r < p.rows ? r : p.rows - 1;
-    return x + r * kvec;
+    return am + r * kvec;
   };
 
-  Moments<NT> st;
   uint4 a[steps], an[steps];
   const uint4* xr = a_row(split);
 #pragma unroll
@@ -122,7 +141,7 @@ __global__ __launch_bounds__(kT) void conv1x1_stats(
       for (int s = 0; s < steps; s++) an[s] = src[2 * s + h];
       if (!RES) {
         __syncthreads();
-        stage_w<NT, KC>(lds, w, n0, p.k, kc, tid);
+        kStageB(lds, w, n0, width, kc, tid);
         __syncthreads();
       }
       const uint4* wl = lds + (RES ? kc * wchunks : 0);
@@ -141,64 +160,86 @@ __global__ __launch_bounds__(kT) void conv1x1_stats(
     }
     xr = xn;
 
-    // rows of this wave's strip that exist
     const int64_t r0 = (int64_t)t * kConvTileRows + wave * 32;
-    const int live = (int)(p.rows - r0 < 32 ? p.rows - r0 : 32);
+    tile_done(t, r0, (int)(p.rows - r0 < 32 ? p.rows - r0 : 32), acc);
+  }
+}
 
-    // registers 2e, 2e+1 (two consecutive rows) rounded into one word
-    unsigned pk[NT][8];
-#pragma unroll
-    for (int j = 0; j < NT; j++)
-#pragma unroll
-      for (int e = 0; e < 8; e++)
-        pk[j][e] = pack_bf16(acc[j][2 * e], acc[j][2 * e + 1]);
+template <int NT, int KC, bool RES>
+__global__ __launch_bounds__(kT) void conv1x1_stats(
+    const uint4* __restrict__ x, const uint4* __restrict__ w,
+    uint4* __restrict__ y, float* __restrict__ part, Conv1x1Plan p) {
+  extern __shared__ uint4 lds[];
+  constexpr int BN = 32 * NT;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int c = lane & 31, h = lane >> 5;
+  const int ntile = conv1x1_ntile(p, blockIdx.x);
+  const int split = conv1x1_split(p, blockIdx.x);
+  const int n0 = ntile * BN;
+  const int nvec = p.n / 8;
+  uint4* stage = lds + (RES ? p.nchunks : 1) * BN * (KC / 8) + wave * 256;
+  unsigned* stage32 = reinterpret_cast<unsigned*>(stage);
 
-    // the moments of the rounded values: what bn_apply will normalise
+  Moments<NT> st;
+  gemm_walk<NT, KC, RES, &stage_w<NT, KC>>(
+      x, w, p.k, n0, lds, p, split, tid, wave, c, h,
+      [&](int, int64_t r0, int live, const f32x16(&acc)[NT])
+          __attribute__((always_inline)) {
+        // registers 2e, 2e+1 (two consecutive rows) rounded into one word
+        unsigned pk[NT][8];
 #pragma unroll
-    for (int e = 0; e < 8; e++) {
-      float lo[NT], hi[NT];
+        for (int j = 0; j < NT; j++)
 #pragma unroll
-      for (int j = 0; j < NT; j++) {
-        lo[j] = __uint_as_float(pk[j][e] << 16);
-        hi[j] = __uint_as_float(pk[j][e] & 0xffff0000u);
-      }
-      if (acc_row(2 * e, h) < live) st.push(lo);
-      if (acc_row(2 * e + 1, h) < live) st.push(hi);
-    }
+          for (int e = 0; e < 8; e++)
+            pk[j][e] = pack_bf16(acc[j][2 * e], acc[j][2 * e + 1]);
 
-    // Two MFMA tiles (64 channels) at a time through the wave's strip: lanes
-    // c and c^1 trade words so that the even lane writes channels (c, c+1) of
-    // row 2e and the odd one channels (c-1, c) of row 2e+1.  Odd rows swap
-    // their 64-byte halves, which keeps both the 4-byte writes and the
-    // 16-byte reads conflict-free.
-    const int odd = c & 1;
-#pragma unroll
-    for (int jp = 0; jp < NT / 2; jp++) {
-#pragma unroll
-      for (int jj = 0; jj < 2; jj++)
+        // the moments of the rounded values: what bn_apply will normalise
 #pragma unroll
         for (int e = 0; e < 8; e++) {
-          const unsigned own = pk[2 * jp + jj][e];
-          // quad_perm [1, 0, 3, 2]
-          const unsigned other = (unsigned)__builtin_amdgcn_update_dpp(
-              0, (int)own, 0xB1, 0xf, 0xf, false);
-          const unsigned word = odd ? (other >> 16) | (own & 0xffff0000u)
-                                    : (own & 0xffffu) | (other << 16);
-          const int row = acc_row(2 * e, h) + odd;
-          stage32[row * 32 + ((jj * 16 + (c >> 1)) ^ ((row & 1) << 4))] = word;
-        }
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
+          float lo[NT], hi[NT];
 #pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const int idx = u * 64 + lane, row = idx >> 3, q = idx & 7;
-        const uint4 v = stage[row * 8 + (q ^ ((row & 1) << 2))];
-        if (row < live) y[(r0 + row) * nvec + (n0 + jp * 64) / 8 + q] = v;
-      }
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
+          for (int j = 0; j < NT; j++) {
+            lo[j] = __uint_as_float(pk[j][e] << 16);
+            hi[j] = __uint_as_float(pk[j][e] & 0xffff0000u);
+          }
+          if (acc_row(2 * e, h) < live) st.push(lo);
+          if (acc_row(2 * e + 1, h) < live) st.push(hi);
+        }
+
+        // Two MFMA tiles (64 channels) at a time through the wave's strip:
+        // lanes c and c^1 trade words so that the even lane writes channels
+        // (c, c+1) of row 2e and the odd one channels (c-1, c) of row 2e+1.
+        // Odd rows swap their 64-byte halves, which keeps both the 4-byte
+        // writes and the 16-byte reads conflict-free.
+        const int odd = c & 1;
+#pragma unroll
+        for (int jp = 0; jp < NT / 2; jp++) {
+#pragma unroll
+          for (int jj = 0; jj < 2; jj++)
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+              const unsigned own = pk[2 * jp + jj][e];
+              // quad_perm [1, 0, 3, 2]
+              const unsigned other = (unsigned)__builtin_amdgcn_update_dpp(
+                  0, (int)own, 0xB1, 0xf, 0xf, false);
+              const unsigned word = odd ? (other >> 16) | (own & 0xffff0000u)
+                                        : (own & 0xffffu) | (other << 16);
+              const int row = acc_row(2 * e, h) + odd;
+              stage32[row * 32 + ((jj * 16 + (c >> 1)) ^ ((row & 1) << 4))] =
+                  word;
+            }
+          asm volatile("" ::: "memory");
+          __builtin_amdgcn_wave_barrier();
+#pragma unroll
+          for (int u = 0; u < 4; u++) {
+            const StripVec s = strip_vec(u, lane, r0, nvec, (n0 + jp * 64) / 8);
+            const uint4 v = stage[s.row * 8 + (s.q ^ ((s.row & 1) << 2))];
+            if (s.row < live) y[s.g] = v;
+          }
+          asm volatile("" ::: "memory");
+          __builtin_amdgcn_wave_barrier();
+        }
+      });
 
   // the eight runs of every channel -> one partial, as a tree
   __syncthreads();
@@ -229,28 +270,6 @@ __global__ __launch_bounds__(kT) void conv1x1_stats(
     row[p.n + n0 + tid] = m[0].m2[0];
     if (tid == 0) row[2 * p.n + ntile] = m[0].n;
   }
-}
-
-template <int NT, int KC, bool RES>
-void launch(const Conv1x1Plan& p, const void* x, const void* w, void* y,
-            float* part, hipStream_t stream) {
-  static const hipError_t attr = hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&conv1x1_stats<NT, KC, RES>),
-      hipFuncAttributeMaxDynamicSharedMemorySize,
-      kConvWLdsBytes + kConvStageBytes);
-  CGX_HIP_CHECK(attr);
-  hipLaunchKernelGGL((conv1x1_stats<NT, KC, RES>), dim3(p.grid), dim3(kT),
-                     p.lds_bytes, stream, static_cast<const uint4*>(x),
-                     static_cast<const uint4*>(w), static_cast<uint4*>(y), part,
-                     p);
-}
-
-template <int NT>
-void launch_nt(const Conv1x1Plan& p, const void* x, const void* w, void* y,
-               float* part, hipStream_t stream) {
-  if (p.kc == 64) launch<NT, 64, true>(p, x, w, y, part, stream);
-  else if (p.resident) launch<NT, 128, true>(p, x, w, y, part, stream);
-  else launch<NT, 128, false>(p, x, w, y, part, stream);
 }
 
 // ---- backward-data ----------------------------------------------------------
@@ -301,159 +320,101 @@ __global__ __launch_bounds__(kT) void conv1x1_bwd_data(
     const uint4* __restrict__ dy, const uint4* __restrict__ w,
     const uint4* __restrict__ skip, uint4* __restrict__ dx, Conv1x1Plan p) {
   extern __shared__ uint4 lds[];
-  constexpr int BN = 32 * NT, cpr = KC / 8, steps = KC / 16;
-  constexpr int wchunks = BN * cpr;
+  constexpr int BN = 32 * NT;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int c = lane & 31, h = lane >> 5;
   const int split = conv1x1_split(p, blockIdx.x);
   const int n0 = conv1x1_ntile(p, blockIdx.x) * BN;
-  const int kvec = p.k / 8, nvec = p.n / 8;
+  const int nvec = p.n / 8;
   // the wave's strip: [32 rows][64 channels] of fp32
-  uint4* stage = lds + (RES ? p.nchunks : 1) * wchunks + wave * 512;
+  uint4* stage = lds + (RES ? p.nchunks : 1) * BN * (KC / 8) + wave * 512;
   float* stagef = reinterpret_cast<float*>(stage);
 
-  if (RES) {
-    for (int kc = 0; kc < p.nchunks; kc++)
-      stage_wt<NT, KC>(lds + kc * wchunks, w, n0, p.n, kc, tid);
-    __syncthreads();
-  }
-
-  auto a_row = [&](int t) {
-    int64_t r = (int64_t)t * kConvTileRows + wave * 32 + c;
-    r = r < p.rows ? r : p.rows - 1;
-    return dy + r * kvec;
-  };
-
-  uint4 a[steps], an[steps];
-  const uint4* xr = a_row(split);
+  gemm_walk<NT, KC, RES, &stage_wt<NT, KC>>(
+      dy, w, p.n, n0, lds, p, split, tid, wave, c, h,
+      [&](int, int64_t r0, int live, const f32x16(&acc)[NT])
+          __attribute__((always_inline)) {
+        // Two MFMA tiles (64 channels) at a time through the strip.  A 4-byte
+        // write goes to bank (row's 64 + channel) % 32 from 32 lanes of one
+        // row: no conflict.  Odd rows swap the 16-byte halves of every 32
+        // bytes, which spreads the 16-byte reads of a lane group (rows r ..
+        // r+3, half a row each) over all 64 banks.
 #pragma unroll
-  for (int s = 0; s < steps; s++) a[s] = xr[2 * s + h];
-
-  for (int i = 0; i < p.tiles_per_split; i++) {
-    const int t = conv1x1_tile(p, split, i);
-    if (t >= p.row_tiles) break;
-    const int tn = conv1x1_tile(p, split, i + 1);
-    const uint4* xn = a_row(tn < p.row_tiles ? tn : t);
-
-    f32x16 acc[NT];
+        for (int jp = 0; jp < NT / 2; jp++) {
+          const int cv = (n0 + jp * 64) / 8;
+          uint4 sk[4];
+          if (ADD) {
 #pragma unroll
-    for (int j = 0; j < NT; j++)
-#pragma unroll
-      for (int e = 0; e < 16; e++) acc[j][e] = 0.f;
-
-    for (int kc = 0; kc < p.nchunks; kc++) {
-      const uint4* src = kc + 1 < p.nchunks ? xr + (kc + 1) * cpr : xn;
-#pragma unroll
-      for (int s = 0; s < steps; s++) an[s] = src[2 * s + h];
-      if (!RES) {
-        __syncthreads();
-        stage_wt<NT, KC>(lds, w, n0, p.n, kc, tid);
-        __syncthreads();
-      }
-      const uint4* wl = lds + (RES ? kc * wchunks : 0);
-#pragma unroll
-      for (int s = 0; s < steps; s++) {
-        const bf16x8 av = __builtin_bit_cast(bf16x8, a[s]);
-#pragma unroll
-        for (int j = 0; j < NT; j++) {
-          const uint4 b = wl[w_slot<KC>(j * 32 + c, 2 * s + h)];
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              av, __builtin_bit_cast(bf16x8, b), acc[j], 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int s = 0; s < steps; s++) a[s] = an[s];
-    }
-    xr = xn;
-
-    const int64_t r0 = (int64_t)t * kConvTileRows + wave * 32;
-    const int live = (int)(p.rows - r0 < 32 ? p.rows - r0 : 32);
-
-    // Two MFMA tiles (64 channels) at a time through the strip.  A 4-byte
-    // write goes to bank (row's 64 + channel) % 32 from 32 lanes of one row:
-    // no conflict.  Odd rows swap the 16-byte halves of every 32 bytes, which
-    // spreads the 16-byte reads of a lane group (rows r .. r+3, half a row
-    // each) over all 64 banks.
-#pragma unroll
-    for (int jp = 0; jp < NT / 2; jp++) {
-      uint4 sk[4];
-      if (ADD) {
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          const int idx = u * 64 + lane, row = idx >> 3, q = idx & 7;
-          sk[u] = make_uint4(0, 0, 0, 0);
-          if (row < live)
-            sk[u] = skip[(r0 + row) * nvec + (n0 + jp * 64) / 8 + q];
-        }
-      }
-#pragma unroll
-      for (int jj = 0; jj < 2; jj++)
-#pragma unroll
-        for (int e = 0; e < 16; e++) {
-          const int row = acc_row(e, h);
-          stagef[row * 64 + ((jj * 32 + c) ^ ((row & 1) << 2))] =
-              acc[2 * jp + jj][e];
-        }
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const int idx = u * 64 + lane, row = idx >> 3, q = idx & 7;
-        const uint4 lo = stage[row * 16 + 2 * q + (row & 1)];
-        const uint4 hi = stage[row * 16 + 2 * q + ((row & 1) ^ 1)];
-        float f[8] = {__uint_as_float(lo.x), __uint_as_float(lo.y),
-                      __uint_as_float(lo.z), __uint_as_float(lo.w),
-                      __uint_as_float(hi.x), __uint_as_float(hi.y),
-                      __uint_as_float(hi.z), __uint_as_float(hi.w)};
-        if (ADD) {
-          const unsigned s4[4] = {sk[u].x, sk[u].y, sk[u].z, sk[u].w};
-#pragma unroll
-          for (int m = 0; m < 4; m++) {
-            f[2 * m] += __uint_as_float(s4[m] << 16);
-            f[2 * m + 1] += __uint_as_float(s4[m] & 0xffff0000u);
+            for (int u = 0; u < 4; u++) {
+              const StripVec s = strip_vec(u, lane, r0, nvec, cv);
+              sk[u] = make_uint4(0, 0, 0, 0);
+              if (s.row < live) sk[u] = skip[s.g];
+            }
           }
+#pragma unroll
+          for (int jj = 0; jj < 2; jj++)
+#pragma unroll
+            for (int e = 0; e < 16; e++) {
+              const int row = acc_row(e, h);
+              stagef[row * 64 + ((jj * 32 + c) ^ ((row & 1) << 2))] =
+                  acc[2 * jp + jj][e];
+            }
+          asm volatile("" ::: "memory");
+          __builtin_amdgcn_wave_barrier();
+#pragma unroll
+          for (int u = 0; u < 4; u++) {
+            const StripVec s = strip_vec(u, lane, r0, nvec, cv);
+            const uint4 lo = stage[s.row * 16 + 2 * s.q + (s.row & 1)];
+            const uint4 hi = stage[s.row * 16 + 2 * s.q + ((s.row & 1) ^ 1)];
+            float f[8] = {__uint_as_float(lo.x), __uint_as_float(lo.y),
+                          __uint_as_float(lo.z), __uint_as_float(lo.w),
+                          __uint_as_float(hi.x), __uint_as_float(hi.y),
+                          __uint_as_float(hi.z), __uint_as_float(hi.w)};
+            if (ADD) {
+              const unsigned s4[4] = {sk[u].x, sk[u].y, sk[u].z, sk[u].w};
+#pragma unroll
+              for (int m = 0; m < 4; m++) {
+                f[2 * m] += __uint_as_float(s4[m] << 16);
+                f[2 * m + 1] += __uint_as_float(s4[m] & 0xffff0000u);
+              }
+            }
+            const uint4 v =
+                make_uint4(pack_bf16(f[0], f[1]), pack_bf16(f[2], f[3]),
+                           pack_bf16(f[4], f[5]), pack_bf16(f[6], f[7]));
+            if (s.row < live) dx[s.g] = v;
+          }
+          asm volatile("" ::: "memory");
+          __builtin_amdgcn_wave_barrier();
         }
-        const uint4 v = make_uint4(pack_bf16(f[0], f[1]), pack_bf16(f[2], f[3]),
-                                   pack_bf16(f[4], f[5]), pack_bf16(f[6], f[7]));
-        if (row < live) dx[(r0 + row) * nvec + (n0 + jp * 64) / 8 + q] = v;
-      }
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
+      });
 }
 
-template <int NT, int KC, bool RES, bool ADD>
-void launch_bwd(const Conv1x1Plan& p, const void* dy, const void* w,
-                const void* skip, void* dx, hipStream_t stream) {
+// f(nt, kc, resident) with the plan's three as integral constants.
+template <typename F>
+void with_tile_constants(const Conv1x1Plan& p, F f) {
+  auto with_nt = [&](auto nt) {
+    using I64 = std::integral_constant<int, 64>;
+    using I128 = std::integral_constant<int, 128>;
+    if (p.kc == 64) f(nt, I64{}, std::true_type{});
+    else if (p.resident) f(nt, I128{}, std::true_type{});
+    else f(nt, I128{}, std::false_type{});
+  };
+  if (p.nt == 2) with_nt(std::integral_constant<int, 2>{});
+  else if (p.nt == 4) with_nt(std::integral_constant<int, 4>{});
+  else with_nt(std::integral_constant<int, 8>{});
+}
+
+// Launches an instantiation of one of the two kernels above, whose waves'
+// strips take kStage bytes; the first launch of each raises its LDS limit.
+template <auto kKernel, int kStage, typename... Args>
+void launch_gemm(const Conv1x1Plan& p, hipStream_t stream, Args... args) {
   static const hipError_t attr = hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&conv1x1_bwd_data<NT, KC, RES, ADD>),
-      hipFuncAttributeMaxDynamicSharedMemorySize,
-      kConvWLdsBytes + kConvBwdStageBytes);
+      reinterpret_cast<const void*>(kKernel),
+      hipFuncAttributeMaxDynamicSharedMemorySize, kConvWLdsBytes + kStage);
   CGX_HIP_CHECK(attr);
-  hipLaunchKernelGGL((conv1x1_bwd_data<NT, KC, RES, ADD>), dim3(p.grid),
-                     dim3(kT), p.lds_bytes, stream,
-                     static_cast<const uint4*>(dy),
-                     static_cast<const uint4*>(w),
-                     static_cast<const uint4*>(skip), static_cast<uint4*>(dx),
-                     p);
-}
-
-template <int NT, bool ADD>
-void launch_bwd_nt(const Conv1x1Plan& p, const void* dy, const void* w,
-                   const void* skip, void* dx, hipStream_t stream) {
-  if (p.kc == 64) launch_bwd<NT, 64, true, ADD>(p, dy, w, skip, dx, stream);
-  else if (p.resident)
-    launch_bwd<NT, 128, true, ADD>(p, dy, w, skip, dx, stream);
-  else launch_bwd<NT, 128, false, ADD>(p, dy, w, skip, dx, stream);
-}
-
-template <bool ADD>
-void launch_bwd_add(const Conv1x1Plan& p, const void* dy, const void* w,
-                    const void* skip, void* dx, hipStream_t stream) {
-  if (p.nt == 2) launch_bwd_nt<2, ADD>(p, dy, w, skip, dx, stream);
-  else if (p.nt == 4) launch_bwd_nt<4, ADD>(p, dy, w, skip, dx, stream);
-  else launch_bwd_nt<8, ADD>(p, dy, w, skip, dx, stream);
+  hipLaunchKernelGGL(kKernel, dim3(p.grid), dim3(kT), p.lds_bytes, stream,
+                     args..., p);
+  CGX_HIP_CHECK(hipGetLastError());
 }
 
 // ---- backward-weights -------------------------------------------------------
@@ -689,18 +650,31 @@ void launch_conv1x1_bwd_data(const Conv1x1Plan& p, const void* dy,
                              const void* w, const void* skip, void* dx,
                              hipStream_t stream) {
   TORCH_CHECK(p.eligible, "conv1x1_bwd_data: shape is not eligible");
-  if (skip) launch_bwd_add<true>(p, dy, w, skip, dx, stream);
-  else launch_bwd_add<false>(p, dy, w, skip, dx, stream);
-  CGX_HIP_CHECK(hipGetLastError());
+  with_tile_constants(p, [&](auto nt, auto kc, auto res) {
+    auto launch = [&](auto add) {
+      launch_gemm<&conv1x1_bwd_data<decltype(nt)::value, decltype(kc)::value,
+                                    decltype(res)::value,
+                                    decltype(add)::value>,
+                  kConvBwdStageBytes>(
+          p, stream, static_cast<const uint4*>(dy),
+          static_cast<const uint4*>(w), static_cast<const uint4*>(skip),
+          static_cast<uint4*>(dx));
+    };
+    if (skip) launch(std::true_type{});
+    else launch(std::false_type{});
+  });
 }
 
 void launch_conv1x1_stats(const Conv1x1Plan& p, const void* x, const void* w,
                           void* y, float* part, hipStream_t stream) {
   TORCH_CHECK(p.eligible, "conv1x1_stats: shape is not eligible");
-  if (p.nt == 2) launch_nt<2>(p, x, w, y, part, stream);
-  else if (p.nt == 4) launch_nt<4>(p, x, w, y, part, stream);
-  else launch_nt<8>(p, x, w, y, part, stream);
-  CGX_HIP_CHECK(hipGetLastError());
+  with_tile_constants(p, [&](auto nt, auto kc, auto res) {
+    launch_gemm<&conv1x1_stats<decltype(nt)::value, decltype(kc)::value,
+                               decltype(res)::value>,
+                kConvStageBytes>(p, stream, static_cast<const uint4*>(x),
+                                 static_cast<const uint4*>(w),
+                                 static_cast<uint4*>(y), part);
+  });
 }
 
 }  // namespace cgx

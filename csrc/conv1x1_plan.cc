@@ -16,6 +16,7 @@ namespace {
 struct Measured {
   int k, n;
   int64_t rows;
+  bool with_add = false;  // backward-data only
 };
 constexpr Measured kNative[] = {
     {64, 64, 802816},   {64, 256, 802816},  {256, 64, 802816},
@@ -23,9 +24,12 @@ constexpr Measured kNative[] = {
     {256, 1024, 50176},
 };
 
-bool measured_faster(int64_t rows, int k, int n) {
-  for (const Measured& m : kNative)
-    if (m.k == k && m.n == n && m.rows == rows) return true;
+template <size_t N>
+bool measured_faster(const Measured (&table)[N], int64_t rows, int64_t k,
+                     int64_t n, bool with_add = false) {
+  for (const Measured& m : table)
+    if (m.k == k && m.n == n && m.rows == rows && m.with_add == with_add)
+      return true;
   return false;
 }
 
@@ -33,29 +37,30 @@ bool pow2_in(int64_t v, int64_t lo, int64_t hi) {
   return v >= lo && v <= hi && (v & (v - 1)) == 0;
 }
 
+// what all three kernels take
+bool shape_ok(int64_t rows, int64_t k, int64_t n) {
+  return pow2_in(k, 64, 2048) && pow2_in(n, 64, 2048) && rows >= 2 &&
+         rows <= kBnMaxRows;
+}
+
+// `max_workgroups` > 0 caps the grid of `tiles` channel tiles
+int64_t cap_splits(int64_t splits, int tiles, int64_t max_workgroups) {
+  if (max_workgroups <= 0) return splits;
+  max_workgroups = std::min<int64_t>(max_workgroups, 1 << 20);
+  return std::min(splits, std::max<int64_t>(1, max_workgroups / tiles));
+}
+
 // The backward-data problems (dX K wide, dY N wide, with or without the skip
 // gradient added) that met the same rule against MIOpen's backward-data plus,
 // with a skip gradient, the bf16 add that follows it (benchmarks/RESULTS.md):
 // the eight of ResNet-50's twelve at batch 256 whose W^T tile stays in LDS.
 // 1024->512 and 2048->512 with the add, 256->1024 and 512->2048 without, lost.
-struct MeasuredBwd {
-  int k, n;
-  int64_t rows;
-  bool with_add;
-};
-constexpr MeasuredBwd kNativeBwd[] = {
+constexpr Measured kNativeBwd[] = {
     {64, 64, 802816, true},    {256, 64, 802816, true},
     {256, 128, 802816, true},  {512, 128, 200704, true},
     {512, 256, 200704, true},  {1024, 256, 50176, true},
     {64, 256, 802816, false},  {128, 512, 200704, false},
 };
-
-bool measured_faster_bwd(int64_t rows, int k, int n, bool with_add) {
-  for (const MeasuredBwd& m : kNativeBwd)
-    if (m.k == k && m.n == n && m.rows == rows && m.with_add == with_add)
-      return true;
-  return false;
-}
 
 // The tiles of a GEMM with p.k contracted and p.n produced; `stage_bytes` of
 // LDS go to the waves' output strips.
@@ -78,10 +83,8 @@ int64_t splits_by_occupancy(const Conv1x1Plan& p, int by_regs) {
                            std::max(1, kConvCus * per_cu / p.ntiles));
 }
 
-void set_grid(Conv1x1Plan& p, int64_t splits, int max_workgroups) {
-  if (max_workgroups > 0)
-    splits = std::min<int64_t>(splits, std::max(1, max_workgroups / p.ntiles));
-  p.splits = (int)splits;
+void set_grid(Conv1x1Plan& p, int64_t splits, int64_t max_workgroups) {
+  p.splits = (int)cap_splits(splits, p.ntiles, max_workgroups);
   p.grid = p.ntiles * p.splits;
   p.tiles_per_split = (p.row_tiles + p.splits - 1) / p.splits;
 }
@@ -97,24 +100,17 @@ constexpr Measured kNativeWrw[] = {
     {512, 2048, 12544}, {2048, 512, 12544},
 };
 
-bool measured_faster_wrw(int64_t rows, int k, int n) {
-  for (const Measured& m : kNativeWrw)
-    if (m.k == k && m.n == n && m.rows == rows) return true;
-  return false;
-}
-
 }  // namespace
 
 Conv1x1WrwPlan conv1x1_wrw_plan(int64_t rows, int64_t k, int64_t n,
-                                int max_workgroups) {
+                                int64_t max_workgroups) {
   Conv1x1WrwPlan p;
   p.rows = rows;
-  p.eligible = pow2_in(k, 64, 2048) && pow2_in(n, 64, 2048) && rows >= 2 &&
-               rows <= kBnMaxRows;
+  p.eligible = shape_ok(rows, k, n);
   if (!p.eligible) return p;
   p.k = (int)k;
   p.n = (int)n;
-  p.native = measured_faster_wrw(rows, p.k, p.n);
+  p.native = measured_faster(kNativeWrw, rows, k, n);
   p.chunk_rows = kWrwChunkRows;
   p.row_chunks = (int)((rows + kWrwChunkRows - 1) / kWrwChunkRows);
   // No more splits than keep the partials, 4*N*K bytes per split written and
@@ -143,9 +139,7 @@ Conv1x1WrwPlan conv1x1_wrw_plan(int64_t rows, int64_t k, int64_t n,
   int64_t splits =
       std::min<int64_t>(cap, std::max(1, kConvCus * per_cu / tiles));
   if (splits > 8) splits -= splits % 8;  // conv1x1_wrw_split
-  if (max_workgroups > 0)
-    splits = std::min<int64_t>(splits, std::max(1, max_workgroups / tiles));
-  p.splits = (int)splits;
+  p.splits = (int)cap_splits(splits, tiles, max_workgroups);
   p.grid = tiles * p.splits;
   p.chunks_per_split = (p.row_chunks + p.splits - 1) / p.splits;
   p.partial_floats = (int64_t)p.splits * p.n * p.k;
@@ -153,15 +147,14 @@ Conv1x1WrwPlan conv1x1_wrw_plan(int64_t rows, int64_t k, int64_t n,
 }
 
 Conv1x1Plan conv1x1_plan(int64_t rows, int64_t k, int64_t n,
-                         int max_workgroups) {
+                         int64_t max_workgroups) {
   Conv1x1Plan p;
   p.rows = rows;
-  p.eligible = pow2_in(k, 64, 2048) && pow2_in(n, 64, 2048) && rows >= 2 &&
-               rows <= kBnMaxRows;
+  p.eligible = shape_ok(rows, k, n);
   if (!p.eligible) return p;
   p.k = (int)k;
   p.n = (int)n;
-  p.native = measured_faster(rows, p.k, p.n);
+  p.native = measured_faster(kNative, rows, k, n);
   tile_geometry(p, kConvStageBytes);
   // no more splits than keep a partial row per split (8*N bytes and the
   // counts) within 5% of the 2*R*N bytes of the output
@@ -178,15 +171,14 @@ Conv1x1Plan conv1x1_plan(int64_t rows, int64_t k, int64_t n,
 }
 
 Conv1x1Plan conv1x1_bwd_plan(int64_t rows, int64_t k, int64_t n, bool with_add,
-                             int max_workgroups) {
+                             int64_t max_workgroups) {
   Conv1x1Plan p;
   p.rows = rows;
-  p.eligible = pow2_in(k, 64, 2048) && pow2_in(n, 64, 2048) && rows >= 2 &&
-               rows <= kBnMaxRows;
+  p.eligible = shape_ok(rows, k, n);
   if (!p.eligible) return p;
   p.k = (int)n;  // contracted: the width of dY
   p.n = (int)k;  // produced: the width of dX
-  p.native = measured_faster_bwd(rows, (int)k, (int)n, with_add);
+  p.native = measured_faster(kNativeBwd, rows, k, n, with_add);
   tile_geometry(p, kConvBwdStageBytes);
   // without the moments the kernel needs fewer registers than the forward:
   // two waves per SIMD with 8 MFMA tiles, three with 4, four with 2, and one

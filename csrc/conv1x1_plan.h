@@ -57,9 +57,10 @@ struct Conv1x1Plan {
 };
 
 // K and N powers of two in [64, 2048], 2 <= R <= 2^24 (as bn_plan).
-// `max_workgroups` > 0 caps the grid.
+// `max_workgroups` > 0 caps the grid; here and below, values above 2^20 count
+// as 2^20.
 Conv1x1Plan conv1x1_plan(int64_t rows, int64_t k, int64_t n,
-                         int max_workgroups = 0);
+                         int64_t max_workgroups = 0);
 
 // Backward-data of the same convolution, dX[R, K] = dY[R, N] * W[N, K], with
 // the skip gradient of a residual fork optionally added in the epilogue
@@ -71,7 +72,7 @@ Conv1x1Plan conv1x1_plan(int64_t rows, int64_t k, int64_t n,
 // stay 0.  `native` comes from this problem's own measurement and depends on
 // `with_add`.
 Conv1x1Plan conv1x1_bwd_plan(int64_t rows, int64_t k, int64_t n, bool with_add,
-                             int max_workgroups = 0);
+                             int64_t max_workgroups = 0);
 
 // Workgroup `wg` owns channels [n0, n0 + bn) and, as its i-th tile, the rows
 // [row0, row1): the walk of the kernel and of the CPU replay.
@@ -130,7 +131,7 @@ struct Conv1x1WrwPlan {
 // K and N powers of two in [64, 2048], 2 <= R <= kBnMaxRows, as the other two.
 // `max_workgroups` > 0 caps the grid.
 Conv1x1WrwPlan conv1x1_wrw_plan(int64_t rows, int64_t k, int64_t n,
-                                int max_workgroups = 0);
+                                int64_t max_workgroups = 0);
 
 // Workgroup `wg` owns channel tile conv1x1_wrw_tile (tile t covers rows
 // (t / ntiles_k) * bn of dW and columns (t % ntiles_k) * bk) and row slice

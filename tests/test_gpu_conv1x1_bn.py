@@ -389,7 +389,7 @@ def test_ineligible_runs_the_stock_convolution(kind, monkeypatch):
 
 
 def test_autograd_function_is_the_convolution():
-    """_Conv1x1Stats under autocast: fp32 master weight in, bf16 kernel, and
+    """_Conv1x1 under autocast: fp32 master weight in, bf16 kernel, and
     the stock convolution's backward.  MIOpen's backward kernels may add in a
     different order from call to call, so the gradients are held to the
     budget above (1.5x the stock path's error against fp64), not to bits."""
@@ -400,7 +400,7 @@ def test_autograd_function_is_the_convolution():
     xa, xb = (x.clone().requires_grad_(True) for _ in range(2))
     wa, wb = (w.clone().requires_grad_(True) for _ in range(2))
     with torch.autocast("cuda", dtype=torch.bfloat16):
-        ya, part = fused_bn._Conv1x1Stats.apply(xa, wa)
+        ya, part, _ = fused_bn._Conv1x1.apply(xa, wa, True, False)
         yb = F.conv2d(xb, wb)
     assert not part.requires_grad and ya.dtype == yb.dtype == torch.bfloat16
     ya.backward(dy)

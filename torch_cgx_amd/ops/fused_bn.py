@@ -19,32 +19,26 @@ BatchNorms at once and its dx pass writes both input gradients.
 tensor and one byte per pooled element (which of the nine window positions
 won), and the backward builds each pixel's gradient from those.
 
-``conv_bn_act(conv, bn, x, ...)`` is ``bn_act(bn, conv(x), ...)``.  Where
-``conv`` is a 1x1 / stride 1 convolution at a shape the plan
-(csrc/conv1x1_plan.cc) has measured faster, the native GEMM kernel
-(csrc/conv1x1_kernels.hip) computes it and hands the BatchNorm the
-per-channel partial statistics of its output, so the statistics pass over
-that output is skipped.  ``identity_conv`` does the same for the downsample
-convolution of a join.  ``CGX_NATIVE_CONV1X1=0`` switches this off,
-``CGX_NATIVE_CONV1X1=all`` takes every shape the kernel accepts, measured
-faster or not.
+``conv_bn_act(conv, bn, x, ...)`` is ``bn_act(bn, conv(x), ...)``, and
+``identity_conv`` the downsample convolution of a join.  A 1x1 / stride 1
+convolution has three native GEMMs (csrc/conv1x1_kernels.hip), each taken at
+the shapes its own table in the plan (csrc/conv1x1_plan.cc) has measured
+faster than the stock path:
 
-The input gradient of such a convolution is the same GEMM with the roles of
-its channels exchanged (``_C.conv1x1_bwd_data``), taken where its own table
-in the plan has measured it faster than the stock backward-data.
-``conv_bn_act_fork`` is ``conv_bn_act`` at the input of a residual block: it
-also returns the tensor the skip path continues from, and the gradient
-arriving over that path is then added in the GEMM's epilogue, not by
-autograd in a pass of its own.
-``CGX_NATIVE_CONV1X1_BWD=0|1|all`` works like the forward switch and is off
-wherever that one is.
+* the forward (``_C.conv1x1_stats``) also hands the BatchNorm the per-channel
+  partial statistics of its output, so the statistics pass is skipped;
+* the input gradient (``_C.conv1x1_bwd_data``) can add a second tensor in
+  its epilogue.  ``conv_bn_act_fork`` is ``conv_bn_act`` at the input of a
+  residual block: it also returns the tensor the skip path continues from,
+  and the gradient arriving over that path is added there, not by autograd
+  in a pass of its own;
+* the weight gradient (``_C.conv1x1_wrw``) splits the rows and sums the
+  fp32 partials in a fixed order: the same bits every run.
 
-The weight gradient is the third GEMM, ``dW = dY^T X`` with the rows
-contracted (``_C.conv1x1_wrw``): a split over the rows whose fp32 partials a
-second kernel sums in a fixed order, so it gives the same bits every run.  It
-too is taken where its own table has measured it faster than the stock
-weight gradient; ``CGX_NATIVE_CONV1X1_WRW=0|1|all`` is its switch, off
-wherever the forward switch is.
+``CGX_NATIVE_CONV1X1``, ``CGX_NATIVE_CONV1X1_BWD`` and
+``CGX_NATIVE_CONV1X1_WRW`` switch them: ``0`` off, ``all`` every shape the
+kernel accepts, measured faster or not.  The two backward switches are off
+wherever the forward one is.
 
 ``CGX_FUSED_BN=0`` switches all native paths off.
 """
@@ -173,41 +167,15 @@ def bn_act(bn: torch.nn.BatchNorm2d, x: torch.Tensor,
     return out
 
 
-class _Conv1x1Stats(torch.autograd.Function):
-    """The 1x1 convolution and the BatchNorm partials of its output; the
-    backward is the stock convolution backward on the same operands, but for
-    the weight gradient where the native one is taken."""
-
-    @staticmethod
-    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
-    def forward(ctx, x, weight):
-        y, part = _C.conv1x1_stats(x, weight)
-        ctx.save_for_backward(x, weight)
-        ctx.mark_non_differentiable(part)
-        return y, part
-
-    @staticmethod
-    @torch.amp.custom_bwd(device_type="cuda")
-    def backward(ctx, dy, _dpart):
-        x, weight = ctx.saved_tensors
-        need_dx, need_dw = ctx.needs_input_grad[:2]
-        if need_dw and _conv1x1_dw_native(dy, x):
-            dw = _conv1x1_dw(dy, x, weight)
-            dx = None
-            if need_dx:
-                dx = _conv1x1_backward(dy, x, weight, (True, False, False))[0]
-            return dx, dw
-        dx, dw, _ = _conv1x1_backward(dy, x, weight, (need_dx, need_dw, False))
-        return dx, dw
-
-
-class _Conv1x1Fork(torch.autograd.Function):
+class _Conv1x1(torch.autograd.Function):
     """``(y, part, skip) = f(x, weight)``: the 1x1 convolution, native with
     partials or stock with ``part`` None as ``native_fwd`` says, and with
     ``fork`` its input once more as ``skip``, for the residual path to go on
     from.  The backward then receives the gradients of both at once, and the
     native backward-data GEMM adds the skip gradient in its epilogue instead
-    of autograd in a pass of its own."""
+    of autograd in a pass of its own.  Each gradient comes from its native
+    GEMM where that is taken; where neither is, both come from one stock
+    convolution backward."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
@@ -226,11 +194,15 @@ class _Conv1x1Fork(torch.autograd.Function):
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, dy, _dpart, dskip):
         x, weight = ctx.saved_tensors
-        dx = dw = None
-        if dy is not None and ctx.needs_input_grad[1]:
-            dw = _conv1x1_dw(dy, x, weight)
-        if ctx.needs_input_grad[0]:
-            dx = dskip if dy is None else _conv1x1_dx(dy, x, weight, dskip)
+        need_dx, need_dw = ctx.needs_input_grad[:2]
+        if dy is None:
+            return (dskip if need_dx else None), None, None, None
+        if (need_dx and need_dw and not _conv1x1_dw_native(dy, x)
+                and not _conv1x1_dx_native(dy, weight, dskip)):
+            dx, dw, _ = _conv1x1_backward(dy, x, weight, (True, True, False))
+            return (dx if dskip is None else dx + dskip), dw, None, None
+        dw = _conv1x1_dw(dy, x, weight) if need_dw else None
+        dx = _conv1x1_dx(dy, x, weight, dskip) if need_dx else None
         return dx, dw, None, None
 
 
@@ -240,12 +212,14 @@ def _conv1x1_backward(dy, x, weight, mask):
 
 
 def _conv1x1_dw_native(dy, x) -> bool:
-    mode = native_conv1x1_wrw_mode()
-    if mode == "0" or not _C.conv1x1_wrw_eligible(dy, x):
-        return False
-    plan = _C.conv1x1_wrw_plan(x.numel() // x.shape[1], x.shape[1],
-                               dy.shape[1])
-    return plan["native"] or mode == "all"
+    return (_C.conv1x1_wrw_eligible(dy, x) and _conv1x1_takes(
+        "wrw", (x.numel() // x.shape[1], x.shape[1], dy.shape[1])))
+
+
+def _conv1x1_dx_native(dy, weight, dskip) -> bool:
+    return (_C.conv1x1_bwd_eligible(dy, weight, dskip) and _conv1x1_takes(
+        "bwd", (dy.numel() // dy.shape[1], weight.shape[1], weight.shape[0]),
+        dskip is not None))
 
 
 def _conv1x1_dw(dy, x, weight):
@@ -259,37 +233,50 @@ def _conv1x1_dw(dy, x, weight):
 def _conv1x1_dx(dy, x, weight, dskip):
     """The input gradient plus ``dskip`` (or None): one native GEMM where the
     plan has measured it faster, else the stock backward-data and a ``+``."""
-    mode = native_conv1x1_bwd_mode()
-    if mode != "0" and _C.conv1x1_bwd_eligible(dy, weight, dskip):
-        plan = _C.conv1x1_bwd_plan(x.numel() // x.shape[1], x.shape[1],
-                                   weight.shape[0], dskip is not None)
-        if plan["native"] or mode == "all":
-            return _C.conv1x1_bwd_data(dy, weight, dskip)
+    if _conv1x1_dx_native(dy, weight, dskip):
+        return _C.conv1x1_bwd_data(dy, weight, dskip)
     dx = _conv1x1_backward(dy, x, weight, (True, False, False))[0]
     return dx if dskip is None else dx + dskip
 
 
-def native_conv1x1_mode() -> str:
-    """"0": off; "all": every eligible shape; else the plan decides."""
-    if not fused_bn_enabled():
+# kernel -> (its switch, its plan in _C)
+_CONV1X1_KERNELS = {
+    "fwd": ("CGX_NATIVE_CONV1X1", "conv1x1_plan"),
+    "bwd": ("CGX_NATIVE_CONV1X1_BWD", "conv1x1_bwd_plan"),
+    "wrw": ("CGX_NATIVE_CONV1X1_WRW", "conv1x1_wrw_plan"),
+}
+
+
+def _conv1x1_mode(kernel: str) -> str:
+    """The switch of the forward ("fwd"), backward-data ("bwd") or
+    backward-weights ("wrw") GEMM.  "0": off; "all": every eligible shape;
+    else the plan decides.  All are off where ``CGX_FUSED_BN`` or the forward
+    switch is."""
+    if not fused_bn_enabled() or os.environ.get("CGX_NATIVE_CONV1X1") == "0":
         return "0"
-    return os.environ.get("CGX_NATIVE_CONV1X1", "1")
+    return os.environ.get(_CONV1X1_KERNELS[kernel][0], "1")
+
+
+def native_conv1x1_mode() -> str:
+    return _conv1x1_mode("fwd")
 
 
 def native_conv1x1_bwd_mode() -> str:
-    """As native_conv1x1_mode, for the backward-data GEMM; off wherever the
-    forward switch is."""
-    if native_conv1x1_mode() == "0":
-        return "0"
-    return os.environ.get("CGX_NATIVE_CONV1X1_BWD", "1")
+    return _conv1x1_mode("bwd")
 
 
 def native_conv1x1_wrw_mode() -> str:
-    """As native_conv1x1_mode, for the backward-weights GEMM; off wherever
-    the forward switch is."""
-    if native_conv1x1_mode() == "0":
-        return "0"
-    return os.environ.get("CGX_NATIVE_CONV1X1_WRW", "1")
+    return _conv1x1_mode("wrw")
+
+
+def _conv1x1_takes(kernel: str, shape, *with_add) -> bool:
+    """Whether ``kernel`` is to run at ``shape`` = (rows, K, N): its switch is
+    on and its plan has measured it faster there, or the switch says "all"."""
+    mode = _conv1x1_mode(kernel)
+    if mode == "0":
+        return False
+    plan = getattr(_C, _CONV1X1_KERNELS[kernel][1])(*shape, *with_add)
+    return plan["eligible"] and (plan["native"] or mode == "all")
 
 
 def _conv1x1_shape(conv, bn, x):
@@ -322,28 +309,6 @@ def _conv1x1_shape(conv, bn, x):
     return x.numel() // x.shape[1], x.shape[1], w.shape[0]
 
 
-def _conv1x1_native(shape) -> bool:
-    plan = _C.conv1x1_plan(*shape)
-    return plan["eligible"] and (plan["native"]
-                                 or native_conv1x1_mode() == "all")
-
-
-def _conv1x1_bwd_native(shape, with_add) -> bool:
-    mode = native_conv1x1_bwd_mode()
-    if mode == "0":
-        return False
-    plan = _C.conv1x1_bwd_plan(*shape, with_add)
-    return plan["eligible"] and (plan["native"] or mode == "all")
-
-
-def _conv1x1_wrw_native(shape) -> bool:
-    mode = native_conv1x1_wrw_mode()
-    if mode == "0":
-        return False
-    plan = _C.conv1x1_wrw_plan(*shape)
-    return plan["eligible"] and (plan["native"] or mode == "all")
-
-
 def _conv(conv, bn, x, fork=False):
     """``(conv(x), part, skip)``: ``part`` are the partials for ``bn``, or
     None where the stock convolution ran; ``skip`` is what a residual path
@@ -352,16 +317,14 @@ def _conv(conv, bn, x, fork=False):
     shape = _conv1x1_shape(conv, bn, x)
     if shape is None:
         return conv(x), None, x
-    fwd = _conv1x1_native(shape)
-    if torch.is_grad_enabled():
-        fork = fork and _conv1x1_bwd_native(shape, True)
-        if (fork or _conv1x1_bwd_native(shape, False)
-                or _conv1x1_wrw_native(shape)):
-            y, part, skip = _Conv1x1Fork.apply(x, conv.weight, fwd, fork)
-            return y, part, (skip if fork else x)
-    if fwd:
-        return _Conv1x1Stats.apply(x, conv.weight) + (x,)
-    return conv(x), None, x
+    fwd = _conv1x1_takes("fwd", shape)
+    grad = torch.is_grad_enabled()
+    fork = fork and grad and _conv1x1_takes("bwd", shape, True)
+    if not (fwd or fork or (grad and (_conv1x1_takes("bwd", shape, False)
+                                      or _conv1x1_takes("wrw", shape)))):
+        return conv(x), None, x
+    y, part, skip = _Conv1x1.apply(x, conv.weight, fwd, fork)
+    return y, part, (skip if fork else x)
 
 
 def conv_bn_act(conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d,
@@ -383,7 +346,7 @@ def conv_bn_act_fork(conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d,
     """``(relu(bn(conv(x))), skip)`` at the input of a residual block:
     ``skip`` has the value of ``x`` and is what the skip path must use in its
     place, so that the path's gradient reaches the convolution's backward
-    (``_Conv1x1Fork``).  Where that does not apply ``skip`` is ``x``."""
+    (``_Conv1x1``).  Where that does not apply ``skip`` is ``x``."""
     y, part, skip = _conv(conv, bn, x, fork=True)
     return bn_act(bn, y, None, relu, part=part), skip
 
