@@ -1100,6 +1100,100 @@ at::Tensor py_conv1x1_bwd_walk(int64_t rows, int64_t k, int64_t n,
   return conv1x1_walk_of(p);
 }
 
+// ---- the tiled walk of both (conv1x1_tiled_plan) ---------------------------
+
+std::tuple<at::Tensor, at::Tensor> py_conv1x1_tiled_stats(
+    const at::Tensor& x, const at::Tensor& weight, int64_t max_workgroups) {
+  TORCH_CHECK(max_workgroups >= 0, "conv1x1_tiled_stats: max_workgroups >= 0");
+  TORCH_CHECK(py_conv1x1_eligible(x, weight),
+              "conv1x1_tiled_stats: input or weight is not eligible");
+  const Conv1x1Plan p = conv1x1_tiled_plan(rows_of(x), x.size(1),
+                                           weight.size(0), max_workgroups);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device().index());
+  auto y = at::empty({x.size(0), p.n, x.size(2), x.size(3)}, x.options(),
+                     at::MemoryFormat::ChannelsLast);
+  auto part = at::empty({p.splits, p.pstride}, x.options().dtype(at::kFloat));
+  launch_conv1x1_tiled_stats(p, x.data_ptr(), weight.data_ptr(), y.data_ptr(),
+                             part.data_ptr<float>(), bn_stream(x));
+  return {y, part};
+}
+
+at::Tensor py_conv1x1_tiled_bwd_data(const at::Tensor& dy,
+                                     const at::Tensor& weight,
+                                     const c10::optional<at::Tensor>& skip,
+                                     int64_t max_workgroups) {
+  TORCH_CHECK(max_workgroups >= 0,
+              "conv1x1_tiled_bwd_data: max_workgroups >= 0");
+  TORCH_CHECK(py_conv1x1_bwd_eligible(dy, weight, skip),
+              "conv1x1_tiled_bwd_data: dy, weight or skip is not eligible");
+  const Conv1x1Plan p =
+      conv1x1_tiled_bwd_plan(rows_of(dy), weight.size(1), weight.size(0),
+                             skip.has_value(), max_workgroups);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dy.device().index());
+  auto dx = at::empty({dy.size(0), p.n, dy.size(2), dy.size(3)}, dy.options(),
+                      at::MemoryFormat::ChannelsLast);
+  launch_conv1x1_tiled_bwd_data(p, dy.data_ptr(), weight.data_ptr(),
+                                skip.has_value() ? skip->data_ptr() : nullptr,
+                                dx.data_ptr(), bn_stream(dy));
+  return dx;
+}
+
+py::dict conv1x1_tiled_plan_dict(const Conv1x1Plan& p) {
+  py::dict d = conv1x1_plan_dict(p);
+  d["tile_rows"] = kTiledTileRows;
+  return d;
+}
+
+py::dict py_conv1x1_tiled_plan(int64_t rows, int64_t k, int64_t n,
+                               int64_t max_workgroups) {
+  const Conv1x1Plan p = conv1x1_tiled_plan(rows, k, n, max_workgroups);
+  py::dict d = conv1x1_tiled_plan_dict(p);
+  d["run"] = p.run;
+  d["partial_stride"] = p.pstride;
+  d["partial_floats"] = p.partial_floats;
+  return d;
+}
+
+py::dict py_conv1x1_tiled_bwd_plan(int64_t rows, int64_t k, int64_t n,
+                                   bool with_add, int64_t max_workgroups) {
+  return conv1x1_tiled_plan_dict(
+      conv1x1_tiled_bwd_plan(rows, k, n, with_add, max_workgroups));
+}
+
+// Test seam: conv1x1_walk_of for the tiled walk's 256-row tiles and its
+// workgroup order.
+at::Tensor conv1x1_tiled_walk_of(const Conv1x1Plan& p) {
+  TORCH_CHECK(p.eligible, "conv1x1_tiled_walk: shape is not eligible");
+  auto out = at::full({p.grid, p.tiles_per_split, 4}, -1,
+                      at::TensorOptions().dtype(at::kLong));
+  int64_t* o = out.data_ptr<int64_t>();
+  for (int wg = 0; wg < p.grid; wg++) {
+    const int split = conv1x1_tiled_split(p, wg);
+    const int nt = conv1x1_tiled_ntile(p, wg);
+    for (int i = 0; i < p.tiles_per_split; i++) {
+      const int t = conv1x1_tile(p, split, i);
+      if (t >= p.row_tiles) break;
+      int64_t* e = o + ((int64_t)wg * p.tiles_per_split + i) * 4;
+      e[0] = (int64_t)t * kTiledTileRows;
+      e[1] = std::min<int64_t>(e[0] + kTiledTileRows, p.rows);
+      e[2] = (int64_t)nt * p.bn;
+      e[3] = e[2] + p.bn;
+    }
+  }
+  return out;
+}
+
+at::Tensor py_conv1x1_tiled_walk(int64_t rows, int64_t k, int64_t n,
+                                 int64_t max_workgroups) {
+  return conv1x1_tiled_walk_of(conv1x1_tiled_plan(rows, k, n, max_workgroups));
+}
+
+at::Tensor py_conv1x1_tiled_bwd_walk(int64_t rows, int64_t k, int64_t n,
+                                     bool with_add, int64_t max_workgroups) {
+  return conv1x1_tiled_walk_of(
+      conv1x1_tiled_bwd_plan(rows, k, n, with_add, max_workgroups));
+}
+
 // ---- 1x1 convolution backward-weights --------------------------------------
 
 // dy and x as the BatchNorm kernels take them, of one batch and image size.
@@ -1398,6 +1492,33 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("max_workgroups") = 0,
         "Test seam: conv1x1_walk for the plan of conv1x1_bwd_plan; channels "
         "are dx's.");
+  m.def("conv1x1_tiled_stats", &cgx::py_conv1x1_tiled_stats, py::arg("x"),
+        py::arg("weight"), py::arg("max_workgroups") = 0,
+        "conv1x1_stats by the tiled walk (256-row tiles, B double-buffered in "
+        "LDS chunk by chunk): the same y bit for bit, partials of the same "
+        "layout.  Takes what conv1x1_eligible admits.");
+  m.def("conv1x1_tiled_bwd_data", &cgx::py_conv1x1_tiled_bwd_data,
+        py::arg("dy"), py::arg("weight"), py::arg("skip") = py::none(),
+        py::arg("max_workgroups") = 0,
+        "conv1x1_bwd_data by the tiled walk: the same dx bit for bit.  Takes "
+        "what conv1x1_bwd_eligible admits.");
+  m.def("conv1x1_tiled_plan", &cgx::py_conv1x1_tiled_plan, py::arg("rows"),
+        py::arg("k"), py::arg("n"), py::arg("max_workgroups") = 0,
+        "The launch geometry of conv1x1_tiled_stats, with the keys of "
+        "conv1x1_plan, and `native`: whether the model uses it at this shape.");
+  m.def("conv1x1_tiled_bwd_plan", &cgx::py_conv1x1_tiled_bwd_plan,
+        py::arg("rows"), py::arg("k"), py::arg("n"),
+        py::arg("with_add") = false, py::arg("max_workgroups") = 0,
+        "The launch geometry of conv1x1_tiled_bwd_data, with the keys of "
+        "conv1x1_bwd_plan.");
+  m.def("conv1x1_tiled_walk", &cgx::py_conv1x1_tiled_walk, py::arg("rows"),
+        py::arg("k"), py::arg("n"), py::arg("max_workgroups") = 0,
+        "Test seam: conv1x1_walk for the plan of conv1x1_tiled_plan.");
+  m.def("conv1x1_tiled_bwd_walk", &cgx::py_conv1x1_tiled_bwd_walk,
+        py::arg("rows"), py::arg("k"), py::arg("n"),
+        py::arg("with_add") = false, py::arg("max_workgroups") = 0,
+        "Test seam: conv1x1_walk for the plan of conv1x1_tiled_bwd_plan; "
+        "channels are dx's.");
   m.def("conv1x1_wrw", &cgx::py_conv1x1_wrw, py::arg("dy"), py::arg("x"),
         py::arg("max_workgroups") = 0,
         "Weight gradient of conv2d(x, weight) for a 1x1 / stride 1 convolution "

@@ -14,6 +14,10 @@
 //       the epilogue turns the tile into 16-byte row vectors through a
 //       per-wave LDS strip of [32 rows][64 channels] and stores them
 //
+// Where B does not stay in LDS a second walk, gemm_walk_tiled, takes over
+// (conv1x1_tiled_stats, conv1x1_tiled_bwd_data): taller tiles and B in two
+// LDS buffers, the same epilogues and the same bits.
+//
 // conv1x1_stats is Y = X * W^T: its epilogue rounds the accumulators to bf16
 // (as bf16_bits does) and the rounded values go into the lane's running
 // moments, so that the output is never read back for the statistics of the
@@ -41,6 +45,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // Where 16-byte chunk q of row n of a [rows][KC] bf16 image sits in LDS.  A
 // B-operand read takes the same q of 16 rows that differ in n & 15; the XOR
@@ -165,23 +170,202 @@ __device__ __forceinline__ void gemm_walk(const uint4* am, const uint4* w,
   }
 }
 
-template <int NT, int KC, bool RES>
-__global__ __launch_bounds__(kT) void conv1x1_stats(
-    const uint4* __restrict__ x, const uint4* __restrict__ w,
-    uint4* __restrict__ y, float* __restrict__ part, Conv1x1Plan p) {
+// ---- the tiled walk ---------------------------------------------------------
+//
+// The same GEMM for shapes whose B tile does not stay in LDS (plan:
+// conv1x1_tiled_plan).  B goes to LDS one [bn, 64] chunk at a time into two
+// buffers: a thread loads its share of chunk g+1 into registers before the
+// MFMAs of chunk g and writes it to the other buffer after them, so the loads
+// are in flight behind the MFMAs and one barrier per chunk orders both
+// buffers.  The tile is 256 rows: a wave owns two 32-row sub-tiles, so every
+// ds_read_b128 of B feeds two MFMAs and every A register NT of them, and the
+// B bytes staged per tile are at most half the A bytes streamed.  Every
+// accumulator is one chain over k in ascending order, as in gemm_walk: the
+// same bits.
+//
+// A Stage is the share of a thread in one chunk of B held in registers:
+// load() reads it from the weight, store() writes it to the swizzled image.
+// StageW / StageWt move exactly what stage_w / stage_wt<NT, 64> move; those
+// two cannot be used here because they wait for their loads before they
+// return.
+template <int NT>
+struct StageW {
+  unsigned v[NT][4];
+  __device__ __forceinline__ void load(const uint4* __restrict__ w, int n0,
+                                       int k, int chunk, int tid) {
+#pragma unroll
+    for (int i = 0; i < NT; i++) {
+      const int idx = tid + i * kT, n = idx / 8, q = idx % 8;
+      const uint4 t = w[((int64_t)(n0 + n) * k + chunk * kTiledKc) / 8 + q];
+      v[i][0] = t.x, v[i][1] = t.y, v[i][2] = t.z, v[i][3] = t.w;
+    }
+  }
+  __device__ __forceinline__ void store(uint4* dst, int tid) const {
+#pragma unroll
+    for (int i = 0; i < NT; i++) {
+      const int idx = tid + i * kT;
+      dst[w_slot<kTiledKc>(idx / 8, idx % 8)] =
+          make_uint4(v[i][0], v[i][1], v[i][2], v[i][3]);
+    }
+  }
+};
+
+constexpr int kTiledSub = kTiledTileRows / kConvTileRows;  // sub-tiles a wave
+
+// tile_done(t, r0, live, acc) is called once per 32-row sub-tile.  All waves
+// of a workgroup run the same tiles and chunks, so each reaches every barrier.
+template <int NT, typename Stage, typename TileDone>
+__device__ __forceinline__ void gemm_walk_tiled(const uint4* am, const uint4* w,
+                                                int width, int n0, uint4* lds,
+                                                const Conv1x1Plan& p, int split,
+                                                int tid, int wave, int c, int h,
+                                                TileDone tile_done) {
+  constexpr int cpr = kTiledKc / 8, steps = kTiledKc / 16;
+  constexpr int wchunks = 32 * NT * cpr;  // 16-byte chunks of one chunk of B
+  const int kvec = p.k / 8;
+
+  // the lane's A row of sub-tile s of row tile t; rows past R read row R-1
+  auto a_row = [&](int t, int s) {
+    int64_t r = (int64_t)t * kTiledTileRows + (wave * kTiledSub + s) * 32 + c;
+    r = r < p.rows ? r : p.rows - 1;
+    return am + r * kvec;
+  };
+
+  Stage b;
+  b.load(w, n0, width, 0, tid);
+  // the A operands of two consecutive chunks: one multiplied, one in flight
+  uint4 a[kTiledSub][steps], an[kTiledSub][steps];
+  const uint4 *xr[kTiledSub], *xn[kTiledSub];
+#pragma unroll
+  for (int s = 0; s < kTiledSub; s++) {
+    xr[s] = a_row(split, s);
+#pragma unroll
+    for (int q = 0; q < steps; q++) a[s][q] = xr[s][2 * q + h];
+  }
+  b.store(lds, tid);
+  // An empty statement that uses the first A operands, so that the wait for
+  // their loads stands here.  Without it every turn of the chunk loop below
+  // waits for its own loads as if they were these.
+#pragma unroll
+  for (int s = 0; s < kTiledSub; s++)
+#pragma unroll
+    for (int q = 0; q < steps; q++) {
+      u32x4 v = {a[s][q].x, a[s][q].y, a[s][q].z, a[s][q].w};
+      asm volatile("" : "+v"(v));
+      a[s][q] = make_uint4(v.x, v.y, v.z, v.w);
+    }
+  int buf = 0;  // the buffer that holds the chunk about to be multiplied
+
+  for (int i = 0; i < p.tiles_per_split; i++) {
+    const int t = conv1x1_tile(p, split, i);
+    if (t >= p.row_tiles) break;
+    const int tn = conv1x1_tile(p, split, i + 1);
+    const bool has_next = tn < p.row_tiles;
+#pragma unroll
+    for (int s = 0; s < kTiledSub; s++) xn[s] = a_row(has_next ? tn : t, s);
+
+    f32x16 acc[kTiledSub][NT];
+#pragma unroll
+    for (int s = 0; s < kTiledSub; s++)
+#pragma unroll
+      for (int j = 0; j < NT; j++)
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc[s][j][e] = 0.f;
+
+    for (int kc = 0; kc < p.nchunks; kc++) {
+      // The next chunk of both operands (of this tile, or the first of the
+      // next tile; the last chunk of the last tile has none) is loaded before
+      // the MFMAs of this one: A into `an`, B into the Stage.
+      const bool last = kc + 1 == p.nchunks;
+      const bool more = !last || has_next;
+#pragma unroll
+      for (int s = 0; s < kTiledSub; s++) {
+        const uint4* src = last ? xn[s] : xr[s] + (kc + 1) * cpr;
+#pragma unroll
+        for (int q = 0; q < steps; q++) an[s][q] = src[2 * q + h];
+      }
+      if (more) b.load(w, n0, width, last ? 0 : kc + 1, tid);
+      // buffer `buf` is written, and the other one, read a chunk ago, is free
+      __syncthreads();
+      const uint4* wl = lds + buf * wchunks;
+      uint4 bv[2][NT];  // the B operands of this 16-deep step and the next
+#pragma unroll
+      for (int j = 0; j < NT; j++)
+        bv[0][j] = wl[w_slot<kTiledKc>(j * 32 + c, h)];
+#pragma unroll
+      for (int q = 0; q < steps; q++) {
+        if (q + 1 < steps)
+#pragma unroll
+          for (int j = 0; j < NT; j++)
+            bv[(q + 1) & 1][j] =
+                wl[w_slot<kTiledKc>(j * 32 + c, 2 * (q + 1) + h)];
+#pragma unroll
+        for (int j = 0; j < NT; j++)
+#pragma unroll
+          for (int s = 0; s < kTiledSub; s++)
+            acc[s][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                __builtin_bit_cast(bf16x8, a[s][q]),
+                __builtin_bit_cast(bf16x8, bv[q & 1][j]), acc[s][j], 0, 0, 0);
+      }
+      // nothing that waits for the loads above may move up among the MFMAs
+      __builtin_amdgcn_sched_barrier(0);
+      buf ^= 1;
+      if (more) b.store(lds + buf * wchunks, tid);
+#pragma unroll
+      for (int s = 0; s < kTiledSub; s++)
+#pragma unroll
+        for (int q = 0; q < steps; q++) a[s][q] = an[s][q];
+    }
+#pragma unroll
+    for (int s = 0; s < kTiledSub; s++) {
+      xr[s] = xn[s];
+      const int64_t r0 =
+          (int64_t)t * kTiledTileRows + (wave * kTiledSub + s) * 32;
+      const int64_t left = p.rows - r0;
+      tile_done(t, r0, (int)(left < 32 ? left : 32), acc[s]);
+    }
+  }
+}
+
+// gemm_walk, or gemm_walk_tiled with `Stage` in place of kStageB.
+template <int NT, int KC, bool RES, bool TILED, auto kStageB, typename Stage,
+          typename TileDone>
+__device__ __forceinline__ void walk(const uint4* am, const uint4* w, int width,
+                                     int n0, uint4* lds, const Conv1x1Plan& p,
+                                     int split, int tid, int wave, int c, int h,
+                                     TileDone tile_done) {
+  if constexpr (TILED)
+    gemm_walk_tiled<NT, Stage>(am, w, width, n0, lds, p, split, tid, wave, c,
+                               h, tile_done);
+  else
+    gemm_walk<NT, KC, RES, kStageB>(am, w, width, n0, lds, p, split, tid, wave,
+                                    c, h, tile_done);
+}
+
+// The forward with either walk: TILED is gemm_walk_tiled, and then KC is
+// kTiledKc and RES false.
+template <int NT, int KC, bool RES, bool TILED>
+__device__ __forceinline__ void stats_body(const uint4* __restrict__ x,
+                                           const uint4* __restrict__ w,
+                                           uint4* __restrict__ y,
+                                           float* __restrict__ part,
+                                           const Conv1x1Plan& p) {
   extern __shared__ uint4 lds[];
   constexpr int BN = 32 * NT;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int c = lane & 31, h = lane >> 5;
-  const int ntile = conv1x1_ntile(p, blockIdx.x);
-  const int split = conv1x1_split(p, blockIdx.x);
+  const int ntile = TILED ? conv1x1_tiled_ntile(p, blockIdx.x)
+                          : conv1x1_ntile(p, blockIdx.x);
+  const int split = TILED ? conv1x1_tiled_split(p, blockIdx.x)
+                          : conv1x1_split(p, blockIdx.x);
   const int n0 = ntile * BN;
   const int nvec = p.n / 8;
-  uint4* stage = lds + (RES ? p.nchunks : 1) * BN * (KC / 8) + wave * 256;
+  uint4* stage =
+      lds + (TILED ? 2 : RES ? p.nchunks : 1) * BN * (KC / 8) + wave * 256;
   unsigned* stage32 = reinterpret_cast<unsigned*>(stage);
 
   Moments<NT> st;
-  gemm_walk<NT, KC, RES, &stage_w<NT, KC>>(
+  walk<NT, KC, RES, TILED, &stage_w<NT, KC>, StageW<NT>>(
       x, w, p.k, n0, lds, p, split, tid, wave, c, h,
       [&](int, int64_t r0, int live, const f32x16(&acc)[NT])
           __attribute__((always_inline)) {
@@ -272,6 +456,20 @@ __global__ __launch_bounds__(kT) void conv1x1_stats(
   }
 }
 
+template <int NT, int KC, bool RES>
+__global__ __launch_bounds__(kT) void conv1x1_stats(
+    const uint4* __restrict__ x, const uint4* __restrict__ w,
+    uint4* __restrict__ y, float* __restrict__ part, Conv1x1Plan p) {
+  stats_body<NT, KC, RES, false>(x, w, y, part, p);
+}
+
+template <int NT>
+__global__ __launch_bounds__(kT) void conv1x1_tiled_stats(
+    const uint4* __restrict__ x, const uint4* __restrict__ w,
+    uint4* __restrict__ y, float* __restrict__ part, Conv1x1Plan p) {
+  stats_body<NT, kTiledKc, false, true>(x, w, y, part, p);
+}
+
 // ---- backward-data ----------------------------------------------------------
 //
 // dX[R, K] = dY[R, N] * W[N, K] is the GEMM above with dY as the A operand and
@@ -315,22 +513,60 @@ __device__ inline void stage_wt(uint4* dst, const uint4* __restrict__ w, int k0,
   }
 }
 
-template <int NT, int KC, bool RES, bool ADD>
-__global__ __launch_bounds__(kT) void conv1x1_bwd_data(
-    const uint4* __restrict__ dy, const uint4* __restrict__ w,
-    const uint4* __restrict__ skip, uint4* __restrict__ dx, Conv1x1Plan p) {
+// stage_wt<NT, 64> in two halves (see StageW): 32*NT threads take a block each.
+template <int NT>
+struct StageWt {
+  unsigned r[8][4];
+  __device__ __forceinline__ void load(const uint4* __restrict__ w, int k0,
+                                       int kw, int chunk, int tid) {
+    if (tid >= 32 * NT) return;
+    const int n8 = tid & 7, k8 = tid >> 3;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      const uint4 v =
+          w[((int64_t)(chunk * kTiledKc + n8 * 8 + i) * kw + k0) / 8 + k8];
+      r[i][0] = v.x, r[i][1] = v.y, r[i][2] = v.z, r[i][3] = v.w;
+    }
+  }
+  __device__ __forceinline__ void store(uint4* dst, int tid) const {
+    if (tid >= 32 * NT) return;
+    const int n8 = tid & 7, k8 = tid >> 3;
+#pragma unroll
+    for (int kk = 0; kk < 8; kk++) {
+      unsigned o[4];
+#pragma unroll
+      for (int m = 0; m < 4; m++) {
+        const unsigned a = r[2 * m][kk >> 1], b = r[2 * m + 1][kk >> 1];
+        o[m] = kk & 1 ? (a >> 16) | (b & 0xffff0000u)
+                      : (a & 0xffffu) | (b << 16);
+      }
+      dst[w_slot<kTiledKc>(k8 * 8 + kk, n8)] =
+          make_uint4(o[0], o[1], o[2], o[3]);
+    }
+  }
+};
+
+template <int NT, int KC, bool RES, bool ADD, bool TILED>
+__device__ __forceinline__ void bwd_data_body(const uint4* __restrict__ dy,
+                                              const uint4* __restrict__ w,
+                                              const uint4* __restrict__ skip,
+                                              uint4* __restrict__ dx,
+                                              const Conv1x1Plan& p) {
   extern __shared__ uint4 lds[];
   constexpr int BN = 32 * NT;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int c = lane & 31, h = lane >> 5;
-  const int split = conv1x1_split(p, blockIdx.x);
-  const int n0 = conv1x1_ntile(p, blockIdx.x) * BN;
+  const int split = TILED ? conv1x1_tiled_split(p, blockIdx.x)
+                          : conv1x1_split(p, blockIdx.x);
+  const int n0 = (TILED ? conv1x1_tiled_ntile(p, blockIdx.x)
+                        : conv1x1_ntile(p, blockIdx.x)) * BN;
   const int nvec = p.n / 8;
   // the wave's strip: [32 rows][64 channels] of fp32
-  uint4* stage = lds + (RES ? p.nchunks : 1) * BN * (KC / 8) + wave * 512;
+  uint4* stage =
+      lds + (TILED ? 2 : RES ? p.nchunks : 1) * BN * (KC / 8) + wave * 512;
   float* stagef = reinterpret_cast<float*>(stage);
 
-  gemm_walk<NT, KC, RES, &stage_wt<NT, KC>>(
+  walk<NT, KC, RES, TILED, &stage_wt<NT, KC>, StageWt<NT>>(
       dy, w, p.n, n0, lds, p, split, tid, wave, c, h,
       [&](int, int64_t r0, int live, const f32x16(&acc)[NT])
           __attribute__((always_inline)) {
@@ -387,6 +623,20 @@ __global__ __launch_bounds__(kT) void conv1x1_bwd_data(
           __builtin_amdgcn_wave_barrier();
         }
       });
+}
+
+template <int NT, int KC, bool RES, bool ADD>
+__global__ __launch_bounds__(kT) void conv1x1_bwd_data(
+    const uint4* __restrict__ dy, const uint4* __restrict__ w,
+    const uint4* __restrict__ skip, uint4* __restrict__ dx, Conv1x1Plan p) {
+  bwd_data_body<NT, KC, RES, ADD, false>(dy, w, skip, dx, p);
+}
+
+template <int NT, bool ADD>
+__global__ __launch_bounds__(kT) void conv1x1_tiled_bwd_data(
+    const uint4* __restrict__ dy, const uint4* __restrict__ w,
+    const uint4* __restrict__ skip, uint4* __restrict__ dx, Conv1x1Plan p) {
+  bwd_data_body<NT, kTiledKc, false, ADD, true>(dy, w, skip, dx, p);
 }
 
 // f(nt, kc, resident) with the plan's three as integral constants.
@@ -675,6 +925,38 @@ void launch_conv1x1_stats(const Conv1x1Plan& p, const void* x, const void* w,
                                  static_cast<const uint4*>(w),
                                  static_cast<uint4*>(y), part);
   });
+}
+
+void launch_conv1x1_tiled_stats(const Conv1x1Plan& p, const void* x,
+                                const void* w, void* y, float* part,
+                                hipStream_t stream) {
+  TORCH_CHECK(p.eligible, "conv1x1_tiled_stats: shape is not eligible");
+  auto launch = [&](auto nt) {
+    launch_gemm<&conv1x1_tiled_stats<decltype(nt)::value>, kConvStageBytes>(
+        p, stream, static_cast<const uint4*>(x), static_cast<const uint4*>(w),
+        static_cast<uint4*>(y), part);
+  };
+  if (p.nt == 2) launch(std::integral_constant<int, 2>{});
+  else launch(std::integral_constant<int, 4>{});
+}
+
+void launch_conv1x1_tiled_bwd_data(const Conv1x1Plan& p, const void* dy,
+                                   const void* w, const void* skip, void* dx,
+                                   hipStream_t stream) {
+  TORCH_CHECK(p.eligible, "conv1x1_tiled_bwd_data: shape is not eligible");
+  auto launch = [&](auto nt, auto add) {
+    launch_gemm<&conv1x1_tiled_bwd_data<decltype(nt)::value,
+                                        decltype(add)::value>,
+                kConvBwdStageBytes>(
+        p, stream, static_cast<const uint4*>(dy), static_cast<const uint4*>(w),
+        static_cast<const uint4*>(skip), static_cast<uint4*>(dx));
+  };
+  auto with_nt = [&](auto nt) {
+    if (skip) launch(nt, std::true_type{});
+    else launch(nt, std::false_type{});
+  };
+  if (p.nt == 2) with_nt(std::integral_constant<int, 2>{});
+  else with_nt(std::integral_constant<int, 4>{});
 }
 
 }  // namespace cgx

@@ -100,7 +100,87 @@ constexpr Measured kNativeWrw[] = {
     {512, 2048, 12544}, {2048, 512, 12544},
 };
 
+// The tiled walk's own tables, by the same rule against the path each problem
+// takes without it: the kernel of kNative / kNativeBwd where that lists the
+// problem, else MIOpen's forward plus bn_stats, or its backward-data plus,
+// with a skip gradient, the bf16 add (benchmarks/RESULTS.md, measured with
+// benchmarks/conv1x1_tiled_shapes.py).  Measured at these row counts only.
+// Forward: the five problems whose W tile does not stay in LDS; where it
+// stays, the resident kernel's ranges overlap this walk's or lie below them.
+constexpr Measured kNativeTiled[] = {
+    {512, 256, 200704},  {1024, 256, 50176}, {1024, 512, 50176},
+    {512, 2048, 12544},  {2048, 512, 12544},
+};
+// Backward-data: all eight problems MIOpen had kept at 14x14 and 7x7 and
+// eight more that kNativeBwd does not list, sixteen of the twenty-four.
+constexpr Measured kNativeTiledBwd[] = {
+    {64, 64, 802816, false},    {64, 256, 802816, true},
+    {256, 64, 802816, false},   {256, 128, 802816, false},
+    {128, 512, 200704, true},   {512, 128, 200704, false},
+    {512, 256, 200704, false},  {256, 1024, 50176, false},
+    {256, 1024, 50176, true},   {1024, 256, 50176, false},
+    {1024, 512, 50176, false},  {1024, 512, 50176, true},
+    {512, 2048, 12544, false},  {512, 2048, 12544, true},
+    {2048, 512, 12544, false},  {2048, 512, 12544, true},
+};
+
+// The geometry both tiled plans share: 256-row tiles of min(n, 128) produced
+// channels, two [bn, 64] chunks of B and the strips in LDS, and the splits a
+// multiple of 8 where there are more than 8 (conv1x1_tiled_split).
+void tiled_geometry(Conv1x1Plan& p, int stage_bytes, int64_t splits_cap,
+                    int64_t max_workgroups) {
+  p.nt = std::min(p.n / 32, kTiledMaxNt);
+  p.bn = 32 * p.nt;
+  p.ntiles = p.n / p.bn;
+  p.kc = kTiledKc;
+  p.nchunks = p.k / p.kc;
+  p.resident = false;
+  p.lds_bytes = 2 * p.bn * p.kc * 2 + stage_bytes;
+  p.row_tiles = (int)((p.rows + kTiledTileRows - 1) / kTiledTileRows);
+  // the registers of a wave with eight accumulator tiles leave one wave per
+  // SIMD, with four two
+  int64_t splits =
+      std::min(splits_by_occupancy(p, p.nt == 4 ? 1 : 2), splits_cap);
+  // ... unless that makes the longest walk a tile longer
+  const int64_t by8 = splits - splits % 8;
+  if (splits > 8 &&
+      (p.row_tiles + by8 - 1) / by8 == (p.row_tiles + splits - 1) / splits)
+    splits = by8;
+  set_grid(p, splits, max_workgroups);
+}
+
 }  // namespace
+
+Conv1x1Plan conv1x1_tiled_plan(int64_t rows, int64_t k, int64_t n,
+                               int64_t max_workgroups) {
+  Conv1x1Plan p;
+  p.rows = rows;
+  p.eligible = shape_ok(rows, k, n);
+  if (!p.eligible) return p;
+  p.k = (int)k;
+  p.n = (int)n;
+  p.native = measured_faster(kNativeTiled, rows, k, n);
+  // the partials within 5% of the output's bytes, as in conv1x1_plan
+  tiled_geometry(p, kConvStageBytes, std::max<int64_t>(1, rows / 82),
+                 max_workgroups);
+  p.run = 32 * p.tiles_per_split;
+  p.pstride = 2 * p.n + p.ntiles;
+  p.partial_floats = (int64_t)p.splits * p.pstride;
+  return p;
+}
+
+Conv1x1Plan conv1x1_tiled_bwd_plan(int64_t rows, int64_t k, int64_t n,
+                                   bool with_add, int64_t max_workgroups) {
+  Conv1x1Plan p;
+  p.rows = rows;
+  p.eligible = shape_ok(rows, k, n);
+  if (!p.eligible) return p;
+  p.k = (int)n;  // contracted: the width of dY
+  p.n = (int)k;  // produced: the width of dX
+  p.native = measured_faster(kNativeTiledBwd, rows, k, n, with_add);
+  tiled_geometry(p, kConvBwdStageBytes, rows, max_workgroups);
+  return p;
+}
 
 Conv1x1WrwPlan conv1x1_wrw_plan(int64_t rows, int64_t k, int64_t n,
                                 int64_t max_workgroups) {

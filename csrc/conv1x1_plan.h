@@ -88,6 +88,38 @@ __host__ __device__ inline int conv1x1_tile(const Conv1x1Plan& p, int split,
   return split + i * p.splits;
 }
 
+// The same two GEMMs for shapes whose B tile does not stay in LDS
+// (gemm_walk_tiled in conv1x1_kernels.hip).  The workgroup's tile is 256 rows
+// x `bn` = min(N, 128) channels: wave w takes rows 64*w .. 64*w+63 as two
+// 32-row sub-tiles, so bn / tile rows <= 1/2.  B is staged one [bn, 64] chunk
+// at a time into two LDS buffers, never resident: `kc` is 64, `resident`
+// false, `lds_bytes` two chunks and the strips.  `run`, the per-lane run of
+// the forward's moments, is 32 rows per tile visited.  The partials have the
+// layout of conv1x1_plan.  `native` is this walk's own measurement against
+// the path the shape takes without it.
+constexpr int kTiledTileRows = 256;
+constexpr int kTiledKc = 64;
+constexpr int kTiledMaxNt = 4;
+
+Conv1x1Plan conv1x1_tiled_plan(int64_t rows, int64_t k, int64_t n,
+                               int64_t max_workgroups = 0);
+Conv1x1Plan conv1x1_tiled_bwd_plan(int64_t rows, int64_t k, int64_t n,
+                                   bool with_add, int64_t max_workgroups = 0);
+
+// Workgroup `wg` of a tiled plan.  The workgroups of one split read the same
+// rows of A once per channel tile, so they are given block indices 8 apart,
+// which land on one XCD and share its L2, wherever the splits divide by 8
+// (as conv1x1_wrw_tile); this is for speed only.  Its i-th row tile is
+// conv1x1_tile, of kTiledTileRows rows.
+__host__ __device__ inline int conv1x1_tiled_ntile(const Conv1x1Plan& p,
+                                                   int wg) {
+  return p.splits % 8 == 0 ? (wg / 8) % p.ntiles : wg % p.ntiles;
+}
+__host__ __device__ inline int conv1x1_tiled_split(const Conv1x1Plan& p,
+                                                   int wg) {
+  return p.splits % 8 == 0 ? (wg / 8 / p.ntiles) * 8 + wg % 8 : wg / p.ntiles;
+}
+
 // The partials of a [splits, 2N + ntiles] buffer as the finalize reads them.
 inline BnPartials conv1x1_partials(const float* part, int n, int splits,
                                    int ntiles) {
@@ -172,5 +204,13 @@ void launch_conv1x1_stats(const Conv1x1Plan& p, const void* x, const void* w,
 void launch_conv1x1_bwd_data(const Conv1x1Plan& p, const void* dy,
                              const void* w, const void* skip, void* dx,
                              hipStream_t stream);
+
+// The two above for a plan of conv1x1_tiled_plan / conv1x1_tiled_bwd_plan.
+void launch_conv1x1_tiled_stats(const Conv1x1Plan& p, const void* x,
+                                const void* w, void* y, float* part,
+                                hipStream_t stream);
+void launch_conv1x1_tiled_bwd_data(const Conv1x1Plan& p, const void* dy,
+                                   const void* w, const void* skip, void* dx,
+                                   hipStream_t stream);
 
 }  // namespace cgx

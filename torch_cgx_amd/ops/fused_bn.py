@@ -35,10 +35,18 @@ faster than the stock path:
 * the weight gradient (``_C.conv1x1_wrw``) splits the rows and sums the
   fp32 partials in a fixed order: the same bits every run.
 
-``CGX_NATIVE_CONV1X1``, ``CGX_NATIVE_CONV1X1_BWD`` and
-``CGX_NATIVE_CONV1X1_WRW`` switch them: ``0`` off, ``all`` every shape the
-kernel accepts, measured faster or not.  The two backward switches are off
-wherever the forward one is.
+The forward and the input gradient each have a second kernel for the shapes
+whose weight tile does not stay in LDS (``_C.conv1x1_tiled_stats``,
+``_C.conv1x1_tiled_bwd_data``: 256-row tiles, the weight double-buffered in
+LDS chunk by chunk).  They give the bits of the first two, have tables of their
+own, and are asked first.
+
+``CGX_NATIVE_CONV1X1``, ``CGX_NATIVE_CONV1X1_BWD``,
+``CGX_NATIVE_CONV1X1_WRW`` and ``CGX_NATIVE_CONV1X1_TILED`` (both tiled
+kernels) switch them: ``0`` off, ``all`` every shape the kernel accepts,
+measured faster or not.  The backward switches and the tiled one are off
+wherever the forward one is, and the tiled input gradient also wherever
+``CGX_NATIVE_CONV1X1_BWD`` is.
 
 ``CGX_FUSED_BN=0`` switches all native paths off.
 """
@@ -169,7 +177,8 @@ def bn_act(bn: torch.nn.BatchNorm2d, x: torch.Tensor,
 
 class _Conv1x1(torch.autograd.Function):
     """``(y, part, skip) = f(x, weight)``: the 1x1 convolution, native with
-    partials or stock with ``part`` None as ``native_fwd`` says, and with
+    partials (``native_fwd`` "tiled": by the tiled kernel) or stock with
+    ``part`` None as ``native_fwd`` says, and with
     ``fork`` its input once more as ``skip``, for the residual path to go on
     from.  The backward then receives the gradients of both at once, and the
     native backward-data GEMM adds the skip gradient in its epilogue instead
@@ -181,7 +190,9 @@ class _Conv1x1(torch.autograd.Function):
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
     def forward(ctx, x, weight, native_fwd, fork):
         if native_fwd:
-            y, part = _C.conv1x1_stats(x, weight)
+            y, part = (_C.conv1x1_tiled_stats(x, weight)
+                       if native_fwd == "tiled"
+                       else _C.conv1x1_stats(x, weight))
             ctx.mark_non_differentiable(part)
         else:
             y, part = F.conv2d(x, weight), None
@@ -216,10 +227,21 @@ def _conv1x1_dw_native(dy, x) -> bool:
         "wrw", (x.numel() // x.shape[1], x.shape[1], dy.shape[1])))
 
 
+def _conv1x1_dx_kernel(dy, weight, dskip):
+    """The native backward-data entry point that takes this problem, the
+    tiled one first, or None."""
+    if not _C.conv1x1_bwd_eligible(dy, weight, dskip):
+        return None
+    shape = (dy.numel() // dy.shape[1], weight.shape[1], weight.shape[0])
+    for kernel, entry in (("tiled_bwd", "conv1x1_tiled_bwd_data"),
+                          ("bwd", "conv1x1_bwd_data")):
+        if _conv1x1_takes(kernel, shape, dskip is not None):
+            return getattr(_C, entry)
+    return None
+
+
 def _conv1x1_dx_native(dy, weight, dskip) -> bool:
-    return (_C.conv1x1_bwd_eligible(dy, weight, dskip) and _conv1x1_takes(
-        "bwd", (dy.numel() // dy.shape[1], weight.shape[1], weight.shape[0]),
-        dskip is not None))
+    return _conv1x1_dx_kernel(dy, weight, dskip) is not None
 
 
 def _conv1x1_dw(dy, x, weight):
@@ -233,8 +255,9 @@ def _conv1x1_dw(dy, x, weight):
 def _conv1x1_dx(dy, x, weight, dskip):
     """The input gradient plus ``dskip`` (or None): one native GEMM where the
     plan has measured it faster, else the stock backward-data and a ``+``."""
-    if _conv1x1_dx_native(dy, weight, dskip):
-        return _C.conv1x1_bwd_data(dy, weight, dskip)
+    kernel = _conv1x1_dx_kernel(dy, weight, dskip)
+    if kernel is not None:
+        return kernel(dy, weight, dskip)
     dx = _conv1x1_backward(dy, x, weight, (True, False, False))[0]
     return dx if dskip is None else dx + dskip
 
@@ -244,15 +267,21 @@ _CONV1X1_KERNELS = {
     "fwd": ("CGX_NATIVE_CONV1X1", "conv1x1_plan"),
     "bwd": ("CGX_NATIVE_CONV1X1_BWD", "conv1x1_bwd_plan"),
     "wrw": ("CGX_NATIVE_CONV1X1_WRW", "conv1x1_wrw_plan"),
+    "tiled_fwd": ("CGX_NATIVE_CONV1X1_TILED", "conv1x1_tiled_plan"),
+    "tiled_bwd": ("CGX_NATIVE_CONV1X1_TILED", "conv1x1_tiled_bwd_plan"),
 }
 
 
 def _conv1x1_mode(kernel: str) -> str:
     """The switch of the forward ("fwd"), backward-data ("bwd") or
-    backward-weights ("wrw") GEMM.  "0": off; "all": every eligible shape;
+    backward-weights ("wrw") GEMM, or of the tiled forward ("tiled_fwd") or
+    backward-data ("tiled_bwd").  "0": off; "all": every eligible shape;
     else the plan decides.  All are off where ``CGX_FUSED_BN`` or the forward
-    switch is."""
+    switch is, the tiled backward-data also where the backward-data one is."""
     if not fused_bn_enabled() or os.environ.get("CGX_NATIVE_CONV1X1") == "0":
+        return "0"
+    if (kernel == "tiled_bwd"
+            and os.environ.get("CGX_NATIVE_CONV1X1_BWD") == "0"):
         return "0"
     return os.environ.get(_CONV1X1_KERNELS[kernel][0], "1")
 
@@ -317,10 +346,16 @@ def _conv(conv, bn, x, fork=False):
     shape = _conv1x1_shape(conv, bn, x)
     if shape is None:
         return conv(x), None, x
-    fwd = _conv1x1_takes("fwd", shape)
+    fwd = ("tiled" if _conv1x1_takes("tiled_fwd", shape)
+           else _conv1x1_takes("fwd", shape))
     grad = torch.is_grad_enabled()
-    fork = fork and grad and _conv1x1_takes("bwd", shape, True)
-    if not (fwd or fork or (grad and (_conv1x1_takes("bwd", shape, False)
+
+    def bwd(with_add):
+        return (_conv1x1_takes("tiled_bwd", shape, with_add)
+                or _conv1x1_takes("bwd", shape, with_add))
+
+    fork = fork and grad and bwd(True)
+    if not (fwd or fork or (grad and (bwd(False)
                                       or _conv1x1_takes("wrw", shape)))):
         return conv(x), None, x
     y, part, skip = _Conv1x1.apply(x, conv.weight, fwd, fork)
