@@ -1271,6 +1271,113 @@ at::Tensor py_conv1x1_wrw_walk(int64_t rows, int64_t k, int64_t n,
   return out;
 }
 
+// ---- 1x1 convolution backward-weights, ring ---------------------------------
+
+bool py_conv1x1_wrw_ring_eligible(const at::Tensor& dy, const at::Tensor& x) {
+  return py_conv1x1_wrw_eligible(dy, x) &&
+         conv1x1_wrw_ring_plan(rows_of(dy), x.size(1), dy.size(1)).eligible;
+}
+
+// as py_conv1x1_wrw, by conv1x1_wrw_ring
+at::Tensor py_conv1x1_wrw_ring(const at::Tensor& dy, const at::Tensor& x,
+                               int64_t max_workgroups) {
+  TORCH_CHECK(max_workgroups >= 0, "conv1x1_wrw_ring: max_workgroups >= 0");
+  TORCH_CHECK(py_conv1x1_wrw_ring_eligible(dy, x),
+              "conv1x1_wrw_ring: dy or x is not eligible");
+  const Conv1x1WrwRingPlan p = conv1x1_wrw_ring_plan(
+      rows_of(dy), x.size(1), dy.size(1), max_workgroups);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dy.device().index());
+  auto dw = at::empty({p.n, p.k, 1, 1}, dy.options(),
+                      at::MemoryFormat::ChannelsLast);
+  auto part = at::empty({p.splits, p.n, p.k}, dy.options().dtype(at::kFloat));
+  launch_conv1x1_wrw_ring(p, dy.data_ptr(), x.data_ptr(),
+                          part.data_ptr<float>(), dw.data_ptr(),
+                          bn_stream(dy));
+  return dw;
+}
+
+py::dict py_conv1x1_wrw_ring_plan(int64_t rows, int64_t k, int64_t n,
+                                  int64_t max_workgroups) {
+  const Conv1x1WrwRingPlan p =
+      conv1x1_wrw_ring_plan(rows, k, n, max_workgroups);
+  py::dict d;
+  d["eligible"] = p.eligible;
+  d["native"] = p.native;
+  d["threads"] = kConvThreads;
+  d["bn"] = p.bn;
+  d["bk"] = p.bk;
+  d["ntiles_n"] = p.ntiles_n;
+  d["ntiles_k"] = p.ntiles_k;
+  d["chunk_rows"] = p.chunk_rows;
+  d["row_chunks"] = p.row_chunks;
+  d["stages"] = p.stages;
+  d["stage_bytes"] = p.stage_bytes;
+  d["splits"] = p.splits;
+  d["grid"] = p.grid;
+  d["chunks_per_split"] = p.chunks_per_split;
+  d["lds_bytes"] = p.lds_bytes;
+  d["partial_floats"] = p.partial_floats;
+  return d;
+}
+
+// Test seams.  The walk as py_conv1x1_wrw_walk ...
+at::Tensor py_conv1x1_wrw_ring_walk(int64_t rows, int64_t k, int64_t n,
+                                    int64_t max_workgroups) {
+  const Conv1x1WrwRingPlan p =
+      conv1x1_wrw_ring_plan(rows, k, n, max_workgroups);
+  TORCH_CHECK(p.eligible, "conv1x1_wrw_ring_walk: shape is not eligible");
+  auto out = at::full({p.grid, p.chunks_per_split, 5}, -1,
+                      at::TensorOptions().dtype(at::kLong));
+  int64_t* o = out.data_ptr<int64_t>();
+  for (int wg = 0; wg < p.grid; wg++) {
+    const int tile = conv1x1_wrw_tile(p, wg), split = conv1x1_wrw_split(p, wg);
+    for (int i = 0; i < p.chunks_per_split; i++) {
+      const int ch = conv1x1_wrw_chunk(p, split, i);
+      if (ch >= p.row_chunks) break;
+      int64_t* e = o + ((int64_t)wg * p.chunks_per_split + i) * 5;
+      e[0] = (int64_t)(tile / p.ntiles_k) * p.bn;
+      e[1] = (int64_t)(tile % p.ntiles_k) * p.bk;
+      e[2] = split;
+      e[3] = (int64_t)ch * p.chunk_rows;
+      e[4] = std::min<int64_t>(e[3] + p.chunk_rows, p.rows);
+    }
+  }
+  return out;
+}
+
+// ... and the fill of one stage replayed on the host.  Entry [operand, wave,
+// j, lane] holds (LDS byte, row of the stage, first channel of the tile) of
+// the 16 bytes that lane `lane` of instruction j of `wave` moves for dY
+// (operand 0) or X (operand 1) into stage `slot`; -1 where the operand has
+// fewer instructions than the other.
+at::Tensor py_conv1x1_wrw_ring_fill(int64_t rows, int64_t k, int64_t n,
+                                    int64_t slot) {
+  const Conv1x1WrwRingPlan p = conv1x1_wrw_ring_plan(rows, k, n);
+  TORCH_CHECK(p.eligible, "conv1x1_wrw_ring_fill: shape is not eligible");
+  TORCH_CHECK(slot >= 0 && slot < p.stages, "conv1x1_wrw_ring_fill: slot");
+  const int waves = kConvThreads / 64;
+  const int most = p.chunk_rows * std::max(p.bn, p.bk) / 2048;
+  auto out = at::full({2, waves, most, 64, 3}, -1,
+                      at::TensorOptions().dtype(at::kLong));
+  int64_t* o = out.data_ptr<int64_t>();
+  for (int op = 0; op < 2; op++) {
+    const int c = op ? p.bk : p.bn;
+    for (int wave = 0; wave < waves; wave++)
+      for (int j = 0; j < p.chunk_rows * c / 2048; j++)
+        for (int lane = 0; lane < 64; lane++) {
+          const WrwImageSlot s = conv1x1_wrw_image_slot(
+              c, conv1x1_wrw_ring_piece(wave, j) + 16 * lane);
+          int64_t* e = o + ((((int64_t)op * waves + wave) * most + j) * 64 +
+                            lane) * 3;
+          e[0] = conv1x1_wrw_ring_lds_base(p, (int)slot, op, wave, j) +
+                 16 * lane;
+          e[1] = s.row;
+          e[2] = s.channel;
+        }
+  }
+  return out;
+}
+
 void py_register_layer(int64_t bucket_idx, int64_t layer_idx, int64_t numel,
                        int64_t bits, int64_t bucket_size) {
   Registry::get().register_layer((int)bucket_idx, (int)layer_idx, numel,
@@ -1525,6 +1632,36 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "on channels_last bf16 tensors: dw[n, k] = bf16(sum_r dy[r, n] * "
         "x[r, k]) as [N, K, 1, 1], accumulated in fp32 in a fixed order and "
         "rounded once.");
+  m.def("conv1x1_wrw_ring", &cgx::py_conv1x1_wrw_ring, py::arg("dy"),
+        py::arg("x"), py::arg("max_workgroups") = 0,
+        "conv1x1_wrw by the kernel that loads the chunks straight into a "
+        "ring of LDS stages; K and N at least 128.");
+  m.def("conv1x1_wrw_ring_eligible", &cgx::py_conv1x1_wrw_ring_eligible,
+        py::arg("dy"), py::arg("x"),
+        "True where conv1x1_wrw_ring takes (dy, x).");
+  m.def("conv1x1_wrw_ring_plan", &cgx::py_conv1x1_wrw_ring_plan,
+        py::arg("rows"), py::arg("k"), py::arg("n"),
+        py::arg("max_workgroups") = 0,
+        "The launch geometry of conv1x1_wrw_ring.");
+  m.def("conv1x1_wrw_ring_walk", &cgx::py_conv1x1_wrw_ring_walk,
+        py::arg("rows"), py::arg("k"), py::arg("n"),
+        py::arg("max_workgroups") = 0,
+        "Test seam: conv1x1_wrw_walk for conv1x1_wrw_ring.");
+  m.def("conv1x1_wrw_ring_fill", &cgx::py_conv1x1_wrw_ring_fill,
+        py::arg("rows"), py::arg("k"), py::arg("n"), py::arg("slot") = 0,
+        "Test seam: (LDS byte, row, channel) of every lane of every load "
+        "that fills one stage of the ring.");
+  m.def("conv1x1_wrw_image_slot",
+        [](int c, int p) {
+          const cgx::WrwImageSlot s = cgx::conv1x1_wrw_image_slot(c, p);
+          return py::make_tuple(s.row, s.channel);
+        },
+        py::arg("c"), py::arg("p"),
+        "Test seam: (row, first channel) at byte p of the LDS image of a "
+        "[64, c] chunk.");
+  m.def("conv1x1_wrw_ring_piece", &cgx::conv1x1_wrw_ring_piece,
+        py::arg("wave"), py::arg("j"),
+        "Test seam: the image byte at which load j of a wave lands.");
   m.def("conv1x1_wrw_eligible", &cgx::py_conv1x1_wrw_eligible, py::arg("dy"),
         py::arg("x"), "True where conv1x1_wrw takes (dy, x).");
   m.def("conv1x1_wrw_plan", &cgx::py_conv1x1_wrw_plan, py::arg("rows"),

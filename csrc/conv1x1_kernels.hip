@@ -858,6 +858,246 @@ __global__ __launch_bounds__(kT) void conv1x1_wrw_finalize(
                        pack_bf16(f[4], f[5]), pack_bf16(f[6], f[7]));
 }
 
+// ---- backward-weights through a ring of LDS stages ---------------------------
+//
+// conv1x1_wrw with the chunks loaded straight into LDS (plan:
+// conv1x1_wrw_ring_plan): the same images, transposed reads and MFMA order,
+// so the same bits at the same tile and splits.  A stage of the ring is the
+// two images of one chunk, filled by global_load_lds_dwordx4: no registers,
+// and kStages stages stay in flight across the barriers.  Per stage:
+//
+//   s_waitcnt vmcnt(N)   the oldest stage of this wave has landed; N counts
+//                        the instructions of the younger ones, kGlds each
+//   s_barrier            ... and that of every wave
+//   ds_read_b64_tr_b16, MFMAs
+//   s_waitcnt lgkmcnt(0), s_barrier   every wave has read the stage
+//   global_load_lds      stage t + kStages into the buffer just freed
+//
+// The loop is unrolled by kStages, so that every LDS address is a constant
+// offset; there is no __syncthreads() and no load into registers while a
+// stage is in flight, and the transposed reads are instructions of the
+// kernel's own (wrw_read_tr), so that the compiler places no vmcnt(0) of its
+// own anywhere in the loop.  A load cannot put zeros in place of rows past R:
+// the chunk with those rows, the last of the workgroup that owns it, is
+// staged through registers as in conv1x1_wrw, once the ring has drained.
+
+typedef __attribute__((address_space(3))) char lds_char;
+typedef __attribute__((address_space(1))) const void global_cvoid;
+
+template <int BN, int BK>
+struct WrwRing {
+  static constexpr int kStageBytes = kWrwChunkRows * (BN + BK) * 2;
+  static constexpr int kStages =
+      kConvLdsBytes / kStageBytes < kWrwRingMaxStages
+          ? kConvLdsBytes / kStageBytes
+          : kWrwRingMaxStages;
+  static constexpr int kGlds = kStageBytes / 4096;  // of a wave, per stage
+  static_assert(kStages >= 2 && (kStages - 1) * kGlds < 64);
+};
+
+template <int N>
+__device__ inline void wait_vmcnt() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+template <int N>
+__device__ inline void wait_lgkmcnt() {
+  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// wrw_operand's read at LDS address `addr` + OFF, as an instruction of the
+// kernel's own.  The compiler orders a ds_read it knows of behind every
+// pending global_load_lds with s_waitcnt vmcnt(0), which would drain the
+// ring at each stage; this one it does not see, so the kernel waits for
+// it itself (lgkmcnt, at most 15) before the MFMAs that take its result.
+// Nothing but source order and the sched_barrier(0) after each wait keeps
+// the MFMAs, and any copy of the result registers, behind that wait: after a
+// change of toolchain read the .s again (the reads must land in the MFMAs'
+// own operand registers, the MFMAs must follow the waits).
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+template <int OFF>
+__device__ inline u32x2 wrw_read_tr(unsigned addr) {
+  static_assert(OFF >= 0 && OFF < 65536);
+  u32x2 v;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2"
+               : "=v"(v)
+               : "v"(addr), "n"(OFF));
+  return v;
+}
+// rows +0 .. +3 in elements 0 .. 3, rows +4 .. +7 in elements 4 .. 7
+__device__ inline bf16x8 wrw_pair(const u32x2 (&v)[2]) {
+  const u32x4 w = {v[0][0], v[0][1], v[1][0], v[1][1]};
+  return __builtin_bit_cast(bf16x8, w);
+}
+
+// the wait before stage t of T: min(T - 1 - t, ST - 1) younger stages stay
+template <int G, int ST>
+__device__ inline void wrw_ring_wait(int left) {
+  if (left >= ST - 1) wait_vmcnt<(ST - 1) * G>();
+  else if (ST > 3 && left == 2) wait_vmcnt<2 * G>();
+  else if (left == 1) wait_vmcnt<G>();
+  else wait_vmcnt<0>();
+}
+
+// The chunk's rows r0 .. r0+63 of channels c0 .. c0+C of src[R, width] into
+// the image at dst, which the wave shares.
+template <int C>
+__device__ inline void wrw_ring_issue(lds_char* dst, const uint4* __restrict__ src,
+                                      int width, int c0, int64_t r0, int wave,
+                                      int lane) {
+  const uint4* base = src + (r0 * width + c0) / 8;
+#pragma unroll
+  for (int j = 0; j < kWrwChunkRows * C / 2048; j++) {
+    const int piece = conv1x1_wrw_ring_piece(wave, j);
+    const WrwImageSlot s = conv1x1_wrw_image_slot(C, piece + 16 * lane);
+    __builtin_amdgcn_global_load_lds(
+        (global_cvoid*)(base + (s.row * width + s.channel) / 8), dst + piece,
+        16, 0, 0);
+  }
+}
+
+template <int BN, int BK>
+__global__ __launch_bounds__(kT) void conv1x1_wrw_ring(
+    const uint4* __restrict__ dy, const uint4* __restrict__ x,
+    float* __restrict__ part, Conv1x1WrwRingPlan p) {
+  extern __shared__ uint4 lds[];
+  using G = WrwRing<BN, BK>;
+  constexpr int MT = BN / 64, KT = BK / 64;  // 32x32 tiles of a wave
+  constexpr int ST = G::kStages, SB = G::kStageBytes;
+  char* ring = reinterpret_cast<char*>(lds);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int c = lane & 31, h = lane >> 5;
+  const int wn = wave >> 1, wk = wave & 1;
+  const int tile = conv1x1_wrw_tile(p, blockIdx.x);
+  const int split = conv1x1_wrw_split(p, blockIdx.x);
+  const int n0 = (tile / p.ntiles_k) * BN, k0 = (tile % p.ntiles_k) * BK;
+
+  // as conv1x1_wrw
+  const int q = (lane >> 2) & 3;
+  const int in_cell = 32 * ((lane >> 4) & 1) + 8 * (lane & 3);
+  int an[MT], ak[KT];
+#pragma unroll
+  for (int j = 0; j < MT; j++)
+    an[j] = wrw_cell<BN>(8 * h + q, wn * MT + j) + in_cell;
+#pragma unroll
+  for (int j = 0; j < KT; j++)
+    ak[j] = wrw_cell<BK>(8 * h + q, wk * KT + j) + in_cell;
+
+  f32x16 acc[MT][KT];
+#pragma unroll
+  for (int jm = 0; jm < MT; jm++)
+#pragma unroll
+    for (int jk = 0; jk < KT; jk++)
+#pragma unroll
+      for (int e = 0; e < 16; e++) acc[jm][jk][e] = 0.f;
+
+  // the chunks split, split + splits, ... below row_chunks; the last one is
+  // left to the end where it has rows past R
+  const int mine = (p.row_chunks - split + p.splits - 1) / p.splits;
+  const bool tail = p.rows % kWrwChunkRows != 0 &&
+                    conv1x1_wrw_chunk(p, split, mine - 1) == p.row_chunks - 1;
+  const int T = mine - (tail ? 1 : 0);
+
+  auto issue = [&](int t, int slot) {
+    const int64_t r0 =
+        (int64_t)conv1x1_wrw_chunk(p, split, t) * kWrwChunkRows;
+    lds_char* dst = (lds_char*)ring + slot * SB;
+    wrw_ring_issue<BN>(dst, dy, p.n, n0, r0, wave, lane);
+    wrw_ring_issue<BK>(dst + kWrwChunkRows * BN * 2, x, p.k, k0, r0, wave,
+                       lane);
+  };
+  // The 16-row steps of the images at LDS addresses img_n and img_k.  The
+  // reads of step s+1 are issued before the MFMAs of step s and waited for
+  // by count, by hand: see wrw_read_tr.
+  const unsigned ring_addr = (unsigned)(unsigned long)(lds_char*)ring;
+  auto steps = [&](unsigned img_n, unsigned img_k) {
+    constexpr int NS = kWrwChunkRows / 16;
+    u32x2 a[2][MT][2], b[2][KT][2];
+    unsigned pn[MT], pk[KT];
+#pragma unroll
+    for (int j = 0; j < MT; j++) pn[j] = img_n + an[j];
+#pragma unroll
+    for (int j = 0; j < KT; j++) pk[j] = img_k + ak[j];
+    auto read = [&](auto step) {
+      constexpr int s = decltype(step)::value;
+#pragma unroll
+      for (int j = 0; j < MT; j++) {
+        a[s & 1][j][0] = wrw_read_tr<s * 32 * BN>(pn[j]);
+        a[s & 1][j][1] = wrw_read_tr<s * 32 * BN + 8 * BN>(pn[j]);
+      }
+#pragma unroll
+      for (int j = 0; j < KT; j++) {
+        b[s & 1][j][0] = wrw_read_tr<s * 32 * BK>(pk[j]);
+        b[s & 1][j][1] = wrw_read_tr<s * 32 * BK + 8 * BK>(pk[j]);
+      }
+    };
+    auto step_at = [&](auto self, auto step) {
+      constexpr int s = decltype(step)::value;
+      if constexpr (s < NS) {
+        if constexpr (s + 1 < NS) {
+          read(std::integral_constant<int, s + 1>{});
+          wait_lgkmcnt<2 * (MT + KT)>();
+        } else {
+          wait_lgkmcnt<0>();
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int jm = 0; jm < MT; jm++)
+#pragma unroll
+          for (int jk = 0; jk < KT; jk++)
+            acc[jm][jk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                wrw_pair(a[s & 1][jm]), wrw_pair(b[s & 1][jk]), acc[jm][jk], 0,
+                0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        self(self, std::integral_constant<int, s + 1>{});
+      }
+    };
+    read(std::integral_constant<int, 0>{});
+    step_at(step_at, std::integral_constant<int, 0>{});
+  };
+
+#pragma unroll
+  for (int s = 0; s < ST; s++)
+    if (s < T) issue(s, s);
+  for (int t0 = 0; t0 < T; t0 += ST) {
+#pragma unroll
+    for (int s = 0; s < ST; s++) {
+      const int t = t0 + s;
+      if (t >= T) break;
+      wrw_ring_wait<G::kGlds, ST>(T - 1 - t);
+      __builtin_amdgcn_s_barrier();
+      steps(ring_addr + s * SB, ring_addr + s * SB + kWrwChunkRows * BN * 2);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      if (t + ST < T) issue(t + ST, s);
+    }
+  }
+  if (tail) {
+    // nothing is in flight and every wave is past its last read
+    uint4 vn[BN / 32], vk[BK / 32];
+    const int64_t r0 = (int64_t)(p.row_chunks - 1) * kWrwChunkRows;
+    wrw_load<BN>(vn, dy, p.n, n0, r0, p.rows, tid);
+    wrw_load<BK>(vk, x, p.k, k0, r0, p.rows, tid);
+    wrw_store<BN>(ring, vn, tid);
+    wrw_store<BK>(ring + kWrwChunkRows * BN * 2, vk, tid);
+    __syncthreads();
+    steps(ring_addr, ring_addr + kWrwChunkRows * BN * 2);
+  }
+
+  float* out = part + (int64_t)split * p.n * p.k;
+#pragma unroll
+  for (int jm = 0; jm < MT; jm++)
+#pragma unroll
+    for (int jk = 0; jk < KT; jk++)
+#pragma unroll
+      for (int e = 0; e < 16; e++) {
+        const int n = n0 + (wn * MT + jm) * 32 + acc_row(e, h);
+        const int k = k0 + (wk * KT + jk) * 32 + c;
+        out[(int64_t)n * p.k + k] = acc[jm][jk][e];
+      }
+}
+
 template <int BN, int BK>
 void launch_wrw(const Conv1x1WrwPlan& p, const void* dy, const void* x,
                 float* part, hipStream_t stream) {
@@ -875,15 +1115,26 @@ void launch_wrw_bn(const Conv1x1WrwPlan& p, const void* dy, const void* x,
   else TORCH_CHECK(false, "conv1x1_wrw: no 256 x 256 tile");
 }
 
-}  // namespace
-
-void launch_conv1x1_wrw(const Conv1x1WrwPlan& p, const void* dy, const void* x,
-                        float* part, void* dw, hipStream_t stream) {
-  TORCH_CHECK(p.eligible, "conv1x1_wrw: shape is not eligible");
-  if (p.bn == 64) launch_wrw_bn<64>(p, dy, x, part, stream);
-  else if (p.bn == 128) launch_wrw_bn<128>(p, dy, x, part, stream);
-  else launch_wrw_bn<256>(p, dy, x, part, stream);
+template <int BN, int BK>
+void launch_wrw_ring(const Conv1x1WrwRingPlan& p, const void* dy,
+                     const void* x, float* part, hipStream_t stream) {
+  using G = WrwRing<BN, BK>;
+  TORCH_CHECK(p.bn == BN && p.bk == BK && p.stages == G::kStages &&
+                  p.lds_bytes == G::kStages * G::kStageBytes,
+              "conv1x1_wrw_ring: plan and kernel disagree on the ring");
+  static const hipError_t attr = hipFuncSetAttribute(
+      reinterpret_cast<const void*>(&conv1x1_wrw_ring<BN, BK>),
+      hipFuncAttributeMaxDynamicSharedMemorySize, kConvLdsBytes);
+  CGX_HIP_CHECK(attr);
+  hipLaunchKernelGGL((conv1x1_wrw_ring<BN, BK>), dim3(p.grid), dim3(kT),
+                     p.lds_bytes, stream, static_cast<const uint4*>(dy),
+                     static_cast<const uint4*>(x), part, p);
   CGX_HIP_CHECK(hipGetLastError());
+}
+
+// the sum of the planes that either kernel wrote
+void launch_wrw_finalize(const Conv1x1WrwPlan& p, const float* part, void* dw,
+                         hipStream_t stream) {
   // lanes per vector: as many as the splits give work to, until the grid
   // has four waves for every SIMD
   const int64_t vecs = (int64_t)p.n * p.k / 8;
@@ -894,6 +1145,26 @@ void launch_conv1x1_wrw(const Conv1x1WrwPlan& p, const void* dy, const void* x,
                      reinterpret_cast<const float4*>(part),
                      static_cast<uint4*>(dw), p.splits, vecs, g);
   CGX_HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace
+
+void launch_conv1x1_wrw(const Conv1x1WrwPlan& p, const void* dy, const void* x,
+                        float* part, void* dw, hipStream_t stream) {
+  TORCH_CHECK(p.eligible, "conv1x1_wrw: shape is not eligible");
+  if (p.bn == 64) launch_wrw_bn<64>(p, dy, x, part, stream);
+  else if (p.bn == 128) launch_wrw_bn<128>(p, dy, x, part, stream);
+  else launch_wrw_bn<256>(p, dy, x, part, stream);
+  CGX_HIP_CHECK(hipGetLastError());
+  launch_wrw_finalize(p, part, dw, stream);
+}
+
+void launch_conv1x1_wrw_ring(const Conv1x1WrwRingPlan& p, const void* dy,
+                             const void* x, float* part, void* dw,
+                             hipStream_t stream) {
+  TORCH_CHECK(p.eligible, "conv1x1_wrw_ring: shape is not eligible");
+  launch_wrw_ring<kWrwRingTile, kWrwRingTile>(p, dy, x, part, stream);
+  launch_wrw_finalize(p, part, dw, stream);
 }
 
 void launch_conv1x1_bwd_data(const Conv1x1Plan& p, const void* dy,

@@ -100,6 +100,16 @@ constexpr Measured kNativeWrw[] = {
     {512, 2048, 12544}, {2048, 512, 12544},
 };
 
+// The backward-weights problems at which conv1x1_wrw_ring met the same rule
+// against conv1x1_wrw, both with the finalize (benchmarks/RESULTS.md,
+// measured with benchmarks/conv1x1_wrw_ring_shapes.py): all nine of the twelve
+// that have 128 channels on both sides.
+constexpr Measured kNativeWrwRing[] = {
+    {256, 128, 802816}, {128, 512, 200704}, {512, 128, 200704},
+    {512, 256, 200704}, {256, 1024, 50176}, {1024, 256, 50176},
+    {1024, 512, 50176}, {512, 2048, 12544}, {2048, 512, 12544},
+};
+
 // The tiled walk's own tables, by the same rule against the path each problem
 // takes without it: the kernel of kNative / kNativeBwd where that lists the
 // problem, else MIOpen's forward plus bn_stats, or its backward-data plus,
@@ -218,6 +228,36 @@ Conv1x1WrwPlan conv1x1_wrw_plan(int64_t rows, int64_t k, int64_t n,
   const int tiles = p.ntiles_n * p.ntiles_k;
   int64_t splits =
       std::min<int64_t>(cap, std::max(1, kConvCus * per_cu / tiles));
+  if (splits > 8) splits -= splits % 8;  // conv1x1_wrw_split
+  p.splits = (int)cap_splits(splits, tiles, max_workgroups);
+  p.grid = tiles * p.splits;
+  p.chunks_per_split = (p.row_chunks + p.splits - 1) / p.splits;
+  p.partial_floats = (int64_t)p.splits * p.n * p.k;
+  return p;
+}
+
+Conv1x1WrwRingPlan conv1x1_wrw_ring_plan(int64_t rows, int64_t k, int64_t n,
+                                         int64_t max_workgroups) {
+  Conv1x1WrwRingPlan p;
+  p.rows = rows;
+  p.eligible = shape_ok(rows, k, n) && k >= 128 && n >= 128;
+  if (!p.eligible) return p;
+  p.k = (int)k;
+  p.n = (int)n;
+  p.native = measured_faster(kNativeWrwRing, rows, k, n);
+  p.chunk_rows = kWrwChunkRows;
+  p.row_chunks = (int)((rows + kWrwChunkRows - 1) / kWrwChunkRows);
+  p.bn = p.bk = kWrwRingTile;
+  p.ntiles_n = p.n / p.bn;
+  p.ntiles_k = p.k / p.bk;
+  p.stage_bytes = p.chunk_rows * (p.bn + p.bk) * 2;
+  p.stages = std::min(kWrwRingMaxStages, kConvLdsBytes / p.stage_bytes);
+  p.lds_bytes = p.stages * p.stage_bytes;
+  // one workgroup per CU: what keeps the loads in flight is the ring, not a
+  // second workgroup, and the partials grow with the splits
+  const int tiles = p.ntiles_n * p.ntiles_k;
+  int64_t splits =
+      std::min<int64_t>(p.row_chunks, std::max(1, kConvCus / tiles));
   if (splits > 8) splits -= splits % 8;  // conv1x1_wrw_split
   p.splits = (int)cap_splits(splits, tiles, max_workgroups);
   p.grid = tiles * p.splits;

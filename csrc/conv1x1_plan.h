@@ -189,10 +189,65 @@ __host__ __device__ inline int conv1x1_wrw_chunk(const Conv1x1WrwPlan& p,
   return split + i * p.splits;
 }
 
+// The same GEMM with the chunks loaded straight into a ring of LDS buffers
+// (conv1x1_wrw_ring in conv1x1_kernels.hip), for the problems whose walk of
+// few, large chunks leaves conv1x1_wrw waiting for memory once per chunk.
+// Chunks, the walk (conv1x1_wrw_tile / _split / _chunk) and the partials are
+// those above, so equal (bn, bk, splits) give equal bits.  The tile is always
+// 128 x 128, so K and N are at least 128: the wider tiles measured no faster
+// (benchmarks/RESULTS.md).  A stage of the ring holds one chunk of both
+// operands, the n image first; `stages` of them are in flight, 128 KiB for
+// one workgroup per CU, and the splits fill the CUs once.  `native` is the
+// ring's own measurement against the path the problem takes without it.
+constexpr int kWrwRingTile = 128;
+constexpr int kWrwRingMaxStages = 4;
+
+struct Conv1x1WrwRingPlan : Conv1x1WrwPlan {
+  int stages = 0;
+  int stage_bytes = 0;  // chunk_rows * (bn + bk) * 2; lds_bytes = stages * it
+};
+
+Conv1x1WrwRingPlan conv1x1_wrw_ring_plan(int64_t rows, int64_t k, int64_t n,
+                                         int64_t max_workgroups = 0);
+
+// A stage is filled by global_load_lds_dwordx4: one instruction of a wave
+// writes 1 KiB of LDS, lane l the 16 bytes at 16*l from a base the wave
+// shares.  So the permutation of the image's cells (wrw_cell in the kernel)
+// goes onto the address each lane loads from: conv1x1_wrw_image_slot is the
+// row of the chunk and the first of the eight channels that the image of a
+// [64 rows][c channels] chunk holds at byte p, a multiple of 16.
+struct WrwImageSlot {
+  int row, channel;
+};
+__host__ __device__ inline WrwImageSlot conv1x1_wrw_image_slot(int c, int p) {
+  const int line = p >> 8, col = (p >> 6) & 3, cells = c / 32;
+  // the row of the line's first cell decides the XOR of the whole line
+  const int swz = c == 64 ? line & 1 : (4 * line / cells) & 3;
+  const int lin = 4 * line + (col ^ swz);
+  return {lin / cells, 32 * (lin % cells) + 8 * ((p >> 4) & 3)};
+}
+// Where the j-th instruction of `wave` for one operand lands, in bytes from
+// the start of that operand's image in the stage: the four waves take
+// consecutive KiB.  An operand of c channels takes 64 * c / 2048 instructions
+// of each wave.
+__host__ __device__ inline int conv1x1_wrw_ring_piece(int wave, int j) {
+  return (4 * j + wave) * 1024;
+}
+// ... and in bytes from the start of LDS, in stage `slot` of the ring;
+// `operand` 0 is dY (bn channels), 1 is X (bk channels).
+__host__ __device__ inline int conv1x1_wrw_ring_lds_base(
+    const Conv1x1WrwRingPlan& p, int slot, int operand, int wave, int j) {
+  return slot * p.stage_bytes + (operand ? p.chunk_rows * p.bn * 2 : 0) +
+         conv1x1_wrw_ring_piece(wave, j);
+}
+
 // dw[N, K] bf16 from dy[R, N] and x[R, K] bf16 through part[splits, N, K]
 // fp32, which needs no initialisation; every pointer 16-byte aligned.
 void launch_conv1x1_wrw(const Conv1x1WrwPlan& p, const void* dy, const void* x,
                         float* part, void* dw, hipStream_t stream);
+void launch_conv1x1_wrw_ring(const Conv1x1WrwRingPlan& p, const void* dy,
+                             const void* x, float* part, void* dw,
+                             hipStream_t stream);
 
 // y[R, N] bf16 and part[splits, pstride] fp32 from x[R, K] and w[N, K] bf16;
 // every pointer 16-byte aligned.

@@ -33,7 +33,11 @@ faster than the stock path:
   and the gradient arriving over that path is added there, not by autograd
   in a pass of its own;
 * the weight gradient (``_C.conv1x1_wrw``) splits the rows and sums the
-  fp32 partials in a fixed order: the same bits every run.
+  fp32 partials in a fixed order: the same bits every run.  For the deep
+  layers, where a workgroup walks few and large chunks, a second kernel
+  (``_C.conv1x1_wrw_ring``) loads them straight into a ring of LDS buffers;
+  it has a table of its own, is asked first, and gives the bits of the first
+  wherever both split the rows alike.
 
 The forward and the input gradient each have a second kernel for the shapes
 whose weight tile does not stay in LDS (``_C.conv1x1_tiled_stats``,
@@ -42,11 +46,12 @@ LDS chunk by chunk).  They give the bits of the first two, have tables of their
 own, and are asked first.
 
 ``CGX_NATIVE_CONV1X1``, ``CGX_NATIVE_CONV1X1_BWD``,
-``CGX_NATIVE_CONV1X1_WRW`` and ``CGX_NATIVE_CONV1X1_TILED`` (both tiled
-kernels) switch them: ``0`` off, ``all`` every shape the kernel accepts,
-measured faster or not.  The backward switches and the tiled one are off
-wherever the forward one is, and the tiled input gradient also wherever
-``CGX_NATIVE_CONV1X1_BWD`` is.
+``CGX_NATIVE_CONV1X1_WRW``, ``CGX_NATIVE_CONV1X1_WRW_RING`` and
+``CGX_NATIVE_CONV1X1_TILED`` (both tiled kernels) switch them: ``0`` off,
+``all`` every shape the kernel accepts, measured faster or not.  The backward
+switches and the tiled one are off wherever the forward one is, the tiled
+input gradient also wherever ``CGX_NATIVE_CONV1X1_BWD`` is, and the ring
+wherever ``CGX_NATIVE_CONV1X1_WRW`` is.
 
 ``CGX_FUSED_BN=0`` switches all native paths off.
 """
@@ -222,9 +227,21 @@ def _conv1x1_backward(dy, x, weight, mask):
         dy, x, weight, None, (1, 1), (0, 0), (1, 1), False, (0, 0), 1, mask)
 
 
+def _conv1x1_dw_kernel(dy, x):
+    """The native backward-weights entry point that takes this problem, the
+    ring first, or None."""
+    if not _C.conv1x1_wrw_eligible(dy, x):
+        return None
+    shape = (x.numel() // x.shape[1], x.shape[1], dy.shape[1])
+    for kernel, entry in (("wrw_ring", "conv1x1_wrw_ring"),
+                          ("wrw", "conv1x1_wrw")):
+        if _conv1x1_takes(kernel, shape):
+            return getattr(_C, entry)
+    return None
+
+
 def _conv1x1_dw_native(dy, x) -> bool:
-    return (_C.conv1x1_wrw_eligible(dy, x) and _conv1x1_takes(
-        "wrw", (x.numel() // x.shape[1], x.shape[1], dy.shape[1])))
+    return _conv1x1_dw_kernel(dy, x) is not None
 
 
 def _conv1x1_dx_kernel(dy, weight, dskip):
@@ -247,8 +264,9 @@ def _conv1x1_dx_native(dy, weight, dskip) -> bool:
 def _conv1x1_dw(dy, x, weight):
     """The weight gradient: the native GEMM where the plan has measured it
     faster, else the stock one."""
-    if _conv1x1_dw_native(dy, x):
-        return _C.conv1x1_wrw(dy, x)
+    kernel = _conv1x1_dw_kernel(dy, x)
+    if kernel is not None:
+        return kernel(dy, x)
     return _conv1x1_backward(dy, x, weight, (False, True, False))[1]
 
 
@@ -267,6 +285,7 @@ _CONV1X1_KERNELS = {
     "fwd": ("CGX_NATIVE_CONV1X1", "conv1x1_plan"),
     "bwd": ("CGX_NATIVE_CONV1X1_BWD", "conv1x1_bwd_plan"),
     "wrw": ("CGX_NATIVE_CONV1X1_WRW", "conv1x1_wrw_plan"),
+    "wrw_ring": ("CGX_NATIVE_CONV1X1_WRW_RING", "conv1x1_wrw_ring_plan"),
     "tiled_fwd": ("CGX_NATIVE_CONV1X1_TILED", "conv1x1_tiled_plan"),
     "tiled_bwd": ("CGX_NATIVE_CONV1X1_TILED", "conv1x1_tiled_bwd_plan"),
 }
@@ -275,10 +294,16 @@ _CONV1X1_KERNELS = {
 def _conv1x1_mode(kernel: str) -> str:
     """The switch of the forward ("fwd"), backward-data ("bwd") or
     backward-weights ("wrw") GEMM, or of the tiled forward ("tiled_fwd") or
-    backward-data ("tiled_bwd").  "0": off; "all": every eligible shape;
-    else the plan decides.  All are off where ``CGX_FUSED_BN`` or the forward
-    switch is, the tiled backward-data also where the backward-data one is."""
+    backward-data ("tiled_bwd") or the ring backward-weights ("wrw_ring").
+    "0": off; "all": every eligible shape; else the plan decides.  All are
+    off where ``CGX_FUSED_BN`` or the forward switch is, the tiled
+    backward-data also where the backward-data one is and the ring
+    backward-weights where the backward-weights one is; "all" is not
+    inherited."""
     if not fused_bn_enabled() or os.environ.get("CGX_NATIVE_CONV1X1") == "0":
+        return "0"
+    if (kernel == "wrw_ring"
+            and os.environ.get("CGX_NATIVE_CONV1X1_WRW") == "0"):
         return "0"
     if (kernel == "tiled_bwd"
             and os.environ.get("CGX_NATIVE_CONV1X1_BWD") == "0"):
@@ -296,6 +321,10 @@ def native_conv1x1_bwd_mode() -> str:
 
 def native_conv1x1_wrw_mode() -> str:
     return _conv1x1_mode("wrw")
+
+
+def native_conv1x1_wrw_ring_mode() -> str:
+    return _conv1x1_mode("wrw_ring")
 
 
 def _conv1x1_takes(kernel: str, shape, *with_add) -> bool:
@@ -356,6 +385,7 @@ def _conv(conv, bn, x, fork=False):
 
     fork = fork and grad and bwd(True)
     if not (fwd or fork or (grad and (bwd(False)
+                                      or _conv1x1_takes("wrw_ring", shape)
                                       or _conv1x1_takes("wrw", shape)))):
         return conv(x), None, x
     y, part, skip = _Conv1x1.apply(x, conv.weight, fwd, fork)
