@@ -320,6 +320,32 @@ void dequantize_slice(const at::Tensor& comp, at::Tensor& out, int64_t bits,
   }
 }
 
+// Zero-filled buffer for the compressed form of x.
+at::Tensor compressed_buffer(const at::Tensor& x, int64_t bits,
+                             int64_t bucket_size, bool skip_incomplete) {
+  const int64_t bytes = buffer_size(x.numel(), dtype_of(x), (int)bits,
+                                    (int)bucket_size, skip_incomplete);
+  return at::zeros({std::max<int64_t>(bytes, 1)},
+                   at::TensorOptions().dtype(at::kByte).device(x.device()));
+}
+
+// Route `slices` and launch every group on the current stream; group k (in
+// routed order) runs with seed + k * seed_step.
+void launch_quantize(const std::vector<QuantSlice>& slices, DType dt,
+                     uint64_t seed, uint64_t seed_step, bool stochastic,
+                     at::Device device) {
+  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(device.index());
+  uint64_t k = 0;
+  for (const QuantGroup& g : route_quantize(slices)) {
+    auto dev = upload(g.descs, g.cum, device);
+    const char* devp = static_cast<const char*>(dev.data_ptr());
+    launch(g, reinterpret_cast<const QuantDesc*>(devp),
+           reinterpret_cast<const int64_t*>(devp +
+                                            sizeof(QuantDesc) * g.descs.size()),
+           dt, seed + (k++) * seed_step, stochastic, stream.stream());
+  }
+}
+
 // Compress a 1-D CUDA tensor; returns the uint8 compressed buffer
 // (zero-filled alignment padding so byte comparisons are well-defined).
 at::Tensor py_quantize(at::Tensor x, int64_t bits, int64_t bucket_size,
@@ -340,23 +366,46 @@ at::Tensor py_quantize(at::Tensor x, int64_t bits, int64_t bucket_size,
   }
   const DType dt = dtype_of(x);
   const int64_t n = x.numel();
-  const int64_t bytes =
-      buffer_size(n, dt, (int)bits, (int)bucket_size, skip_incomplete);
-  auto out = at::zeros({std::max<int64_t>(bytes, 1)},
-                       at::TensorOptions().dtype(at::kByte).device(x.device()));
-  auto stream =
-      c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x.device().index());
-  for (const QuantGroup& g : route_quantize({QuantSlice{
-           x.data_ptr(), out.data_ptr<uint8_t>(), fbp, n, (int)bits,
-           (int)bucket_size, skip_incomplete}})) {
-    auto dev = upload(g.descs, g.cum, x.device());
-    const char* devp = static_cast<const char*>(dev.data_ptr());
-    launch(g, reinterpret_cast<const QuantDesc*>(devp),
-           reinterpret_cast<const int64_t*>(devp +
-                                            sizeof(QuantDesc) * g.descs.size()),
-           dt, (uint64_t)seed, stochastic, stream.stream());
-  }
+  auto out = compressed_buffer(x, bits, bucket_size, skip_incomplete);
+  launch_quantize({QuantSlice{x.data_ptr(), out.data_ptr<uint8_t>(), fbp, n,
+                              (int)bits, (int)bucket_size, skip_incomplete}},
+                  dt, (uint64_t)seed, /*seed_step=*/0, stochastic, x.device());
   return out;
+}
+
+// Test seam for the slice index of the stochastic hash key: compress several
+// 1-D CUDA tensors of one dtype with ONE route_quantize call, so a launch
+// group holds more than one slice, and give group k (in routed order) the
+// seed `seed + k`, as Engine::run_quantize does with seed_++.  Returns one
+// compressed buffer per tensor.
+std::vector<at::Tensor> py_quantize_slices(std::vector<at::Tensor> xs,
+                                           std::vector<int64_t> bits,
+                                           std::vector<int64_t> bucket_sizes,
+                                           bool stochastic, int64_t seed,
+                                           bool skip_incomplete) {
+  TORCH_CHECK(!xs.empty() && bits.size() == xs.size() &&
+                  bucket_sizes.size() == xs.size(),
+              "quantize_slices: one bits and one bucket_size per tensor");
+  std::vector<QuantSlice> slices;
+  std::vector<at::Tensor> outs;
+  for (size_t i = 0; i < xs.size(); i++) {
+    const at::Tensor& x = xs[i];
+    TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 1 &&
+                    x.numel() > 0 && x.device() == xs[0].device() &&
+                    x.scalar_type() == xs[0].scalar_type(),
+                "quantize_slices: non-empty 1-D contiguous CUDA tensors of "
+                "one dtype on one device");
+    TORCH_CHECK(bits[i] >= 1 && bits[i] <= 8, "quantize_slices: bits in [1,8]");
+    TORCH_CHECK(bucket_sizes[i] >= 1, "quantize_slices: bucket_size >= 1");
+    outs.push_back(
+        compressed_buffer(x, bits[i], bucket_sizes[i], skip_incomplete));
+    slices.push_back(QuantSlice{x.data_ptr(), outs[i].data_ptr<uint8_t>(),
+                                nullptr, x.numel(), (int)bits[i],
+                                (int)bucket_sizes[i], skip_incomplete});
+  }
+  launch_quantize(slices, dtype_of(xs[0]), (uint64_t)seed, /*seed_step=*/1,
+                  stochastic, xs[0].device());
+  return outs;
 }
 
 // Decompress `comp` into `out` (1-D CUDA tensor of n elements); add=True
@@ -1494,6 +1543,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bucket_size"), py::arg("stochastic") = false,
         py::arg("seed") = 0, py::arg("skip_incomplete") = false,
         py::arg("feedback") = py::none());
+  m.def("quantize_slices", &cgx::py_quantize_slices, py::arg("xs"),
+        py::arg("bits"), py::arg("bucket_sizes"), py::arg("stochastic"),
+        py::arg("seed"), py::arg("skip_incomplete") = false,
+        "Test seam: compress several 1-D CUDA tensors through one "
+        "route_quantize call; launch group k runs with seed + k.");
   m.def("dequantize", &cgx::py_dequantize, py::arg("comp"), py::arg("out"),
         py::arg("bits"), py::arg("bucket_size"), py::arg("add") = false,
         py::arg("skip_incomplete") = false);

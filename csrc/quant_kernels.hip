@@ -61,8 +61,12 @@ constexpr int kWave = 64;
 constexpr int kMaxBlocks = 4096;  // 256 CU * 8 blocks/CU * 2
 
 // One splitmix64-style hash per 8-value pack; each element draws 8 bits of
-// uniform randomness ([0,1) in steps of 1/256 -- rounding bias <= 1/512 of a
-// quantization unit, negligible vs. the unit-sized quantization error).
+// uniform randomness ([0,1) in steps of 1/256: a fraction f rounds up with
+// probability floor(256 f)/256, so the rounding bias per element lies in
+// (-1/256, 0] of a quantization unit, -1/512 on average -- negligible vs. the
+// unit-sized quantization error).  torch_cgx_amd/ops/golden.py models the
+// hash (pack_rand_words / stochastic_rand); tests/test_gpu_stochastic.py
+// holds every kernel to it byte for byte.
 __device__ __forceinline__ uint64_t rand_pack(uint64_t seed, uint64_t key) {
   uint64_t z = seed + key * 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;

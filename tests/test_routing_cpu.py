@@ -207,6 +207,63 @@ def test_quantize_pinned_variants():
     assert groups[0][5] == 4  # bucket 2048: 4 groups per lane
 
 
+def _routes(n, bucket, bits=4, in_ptr=0x1000, fb=0, skip=False):
+    groups = _C.route_quantize([(in_ptr, 0x2000, fb, n, bits, bucket, skip)])
+    return [(kind, cum, [d[5] for d in descs], gpl)
+            for _, kind, descs, cum, _, gpl in groups]
+
+
+def test_stochastic_suite_routes():
+    """Every shape of tests/test_gpu_stochastic.py lands in the kernel it is
+    listed under there (its tables are imported, not copied)."""
+    import test_gpu_stochastic as st
+    gpls = {512: 1, 1024: 2, 1536: 3, 2048: 4, 520: 2, 24: 1, 1000: 2}
+    assert {b for _, b in st.FAST_SHAPES} == set(gpls)
+    for n, bucket in st.FAST_SHAPES:
+        assert n % bucket == 0 and n // bucket >= 2
+        full = [0, n // bucket]
+        assert _routes(n, bucket) == [(FAST, full, [0], gpls[bucket])]
+        assert _routes(n + st.FAST_TAIL, bucket) == [
+            (FAST, full, [0], gpls[bucket]), (GENERIC, [0, 1], [TAIL], 1)]
+    assert [b // 8 for b in st.SUB_BUCKETS] == [1, 2, 4, 8, 16, 32]
+    for n, bucket in st.sub_shapes():
+        want = [(SUB, [0, 5], [0], 1)]
+        if n % bucket:
+            want.insert(0, (GENERIC, [0, 1], [TAIL], 1))
+        assert _routes(n, bucket) == want
+    n, bucket = st.SUB_BIG
+    assert _routes(n, bucket) == [(SUB, [0, n // bucket], [0], 1)]
+    assert n // bucket > 4096 * 4  # more buckets than waves in the largest grid
+    for n, bucket in st.GENERIC_SHAPES:
+        assert n < bucket or bucket > 2048
+        assert _routes(n, bucket) == [
+            (GENERIC, [0, _ceil(n, bucket)], [0], 1)]
+    for n, bucket in st.UNALIGNED_SHAPES:
+        for es in (2, 4):  # one element past a 16-byte boundary
+            assert _routes(n, bucket, in_ptr=0x1000 + es) == [
+                (GENERIC, [0, _ceil(n, bucket)], [0], 1)]
+    for n, bucket in st.EF_SHAPES:
+        assert _routes(n, bucket, fb=0x3000) == [
+            (GENERIC, [0, _ceil(n, bucket)], [0], 1)]
+    for n, bucket in st.TWO_PASS_SHAPES:
+        assert _routes(n, bucket) == [
+            (TWO_PASS, [0, _ceil(n, bucket)], [0], 1)]
+    assert [_routes(n, b, skip=True) for n, b in st.SKIP_SHAPES] == [
+        [(FAST, [0, 1], [SKIP], 1)], [(SUB, [0, 16], [SKIP], 1)],
+        [(GENERIC, [0, 0], [SKIP], 1)]]
+    # one shape per kernel for the wide packs, every width
+    for bits in st.WIDE_BITS:
+        assert [[r[0] for r in _routes(n, b, bits)]
+                for n, b in st.WIDE_SHAPES] == [
+            [FAST, GENERIC], [GENERIC, SUB], [GENERIC], [TWO_PASS]]
+    # two slices of one shape share one launch group, per kind
+    assert [[r[0] for r in _routes(n, b)] for n, b in st.TWIN_SHAPES] == [
+        [FAST], [SUB], [GENERIC], [TWO_PASS]]
+    # the four slices of one call: fast + tail, sub, two-pass
+    assert [[r[0] for r in _routes(n, b)] for n, b in st.MULTI_SLICES] == [
+        [FAST], [FAST, GENERIC], [SUB], [TWO_PASS]]
+
+
 # ---------------------------------------------------------------------------
 # dequantize
 # ---------------------------------------------------------------------------

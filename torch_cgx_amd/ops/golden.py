@@ -3,8 +3,16 @@
 This is the single source of truth for the compressed wire format used by the
 whole framework.  The HIP/CDNA4 kernels (csrc/quant_kernels.hip), the C++
 engine, and the CPU simulation of the reducers are all tested against this
-model, and in deterministic-rounding mode the GPU kernels must match it
-byte-for-byte.
+model, and the GPU kernels must match it byte-for-byte in BOTH rounding
+modes: deterministic (``rand = 0.5``) and stochastic, where the kernels'
+stateless hash is modelled here (``pack_rand_words`` / ``stochastic_rand``).
+
+Stochastic rounding draws one 64-bit word per pack of 8 values,
+``splitmix64_mix(seed + key * 0x9E3779B97F4A7C15)`` with
+``key = (slice index in its launch group << 44) | pack index in the slice``
+(all mod 2**64), and element ``j`` of the pack uses byte ``j`` of the word:
+``rand = byte / 256``.  The pack index is slice-global, so which kernel
+encodes a pack does not change its bytes.
 
 Wire format (parity with the reference implementation,
 /root/reference/src/common/compression/cuda_compression_operations.cu:68-96,
@@ -70,6 +78,41 @@ def buffer_size(n: int, dtype: torch.dtype, bits: int, bucket_size: int,
     meta = 2 * nb * es
     packed = (n * bits + 7) // 8
     return meta + align8(packed) + residuals * es
+
+
+_U64 = (1 << 64) - 1
+SLICE_SHIFT = 44  # hash key = (slice index << 44) | pack index
+
+
+def pack_rand_words(seed: int, slice_idx: int, first_pack: int,
+                    npacks: int) -> np.ndarray:
+    """The kernels' rand_pack(seed, (slice_idx << 44) | pack) for packs
+    first_pack .. first_pack + npacks - 1, as np.uint64 (arithmetic mod 2**64;
+    seed is taken mod 2**64, as the int64 -> uint64 cast of the binding)."""
+    key = (np.uint64((int(slice_idx) << SLICE_SHIFT) & _U64) |
+           (np.uint64(first_pack) + np.arange(npacks, dtype=np.uint64)))
+    with np.errstate(over="ignore"):
+        z = np.uint64(int(seed) & _U64) + key * np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def rand_from_words(words: np.ndarray, n: int) -> torch.Tensor:
+    """rand_lane over whole packs: element i draws byte i % 8 of word i // 8,
+    as a float32 in [0, 1) in steps of 1/256; the first n elements."""
+    by = (words[:, None] >> (np.uint64(8) * np.arange(8, dtype=np.uint64))) \
+        & np.uint64(0xFF)
+    r = by.astype(np.float32).reshape(-1)[:n] * np.float32(1.0 / 256.0)
+    return torch.from_numpy(np.ascontiguousarray(r))
+
+
+def stochastic_rand(seed: int, n: int, slice_idx: int = 0) -> torch.Tensor:
+    """Per-element rounding offsets of a stochastic quantize of an n-element
+    slice at index slice_idx of its launch group (float32, length n)."""
+    return rand_from_words(
+        pack_rand_words(seed, slice_idx, 0, (n + PACK_SIZE - 1) // PACK_SIZE),
+        n)
 
 
 def compute_meta(x: torch.Tensor, bits: int, bucket_size: int) -> torch.Tensor:
@@ -197,7 +240,9 @@ def quantize(x: torch.Tensor, bits: int, bucket_size: int,
         total = buffer_size(n, x.dtype, bits, bucket_size, True)
         out = torch.zeros(total, dtype=torch.uint8)
         if nq:
-            head = quantize(x[:nq], bits, bucket_size, rand)
+            # a per-element rand covers the head only: the raw tail draws none
+            head_rand = rand[:nq] if isinstance(rand, torch.Tensor) else rand
+            head = quantize(x[:nq], bits, bucket_size, head_rand)
             out[: head.numel()] = head
         if r:
             rb = _raw_bytes(x[nq:])
