@@ -22,6 +22,7 @@
 #include "bn_plan.h"
 #include "collectives.h"
 #include "conv1x1_plan.h"
+#include "conv3x3_plan.h"
 #include "reducer.h"
 
 namespace cgx {
@@ -1293,6 +1294,77 @@ py::dict py_conv1x1_wrw_plan(int64_t rows, int64_t k, int64_t n,
   return d;
 }
 
+// ---- 3x3 convolution backward-weights ---------------------------------------
+
+Conv3x3WrwPlan conv3x3_wrw_plan_of(const at::Tensor& dy, const at::Tensor& x,
+                                   int64_t max_workgroups = 0) {
+  return conv3x3_wrw_plan(x.size(0), x.size(2), x.size(3), x.size(1),
+                          dy.size(1), max_workgroups);
+}
+
+// dy and x as the BatchNorm kernels take them, of one batch and image size.
+bool py_conv3x3_wrw_eligible(const at::Tensor& dy, const at::Tensor& x) {
+  return bn_tensor_ok(dy) && bn_tensor_ok(x) && x.device() == dy.device() &&
+         x.size(0) == dy.size(0) && x.size(2) == dy.size(2) &&
+         x.size(3) == dy.size(3) && conv3x3_wrw_plan_of(dy, x).eligible;
+}
+
+// Gradient of conv2d(x, weight, padding=1) for the [N, C, 3, 3] weight:
+// (dy, x) -> dw
+at::Tensor py_conv3x3_wrw(const at::Tensor& dy, const at::Tensor& x,
+                          int64_t max_workgroups) {
+  TORCH_CHECK(max_workgroups >= 0, "conv3x3_wrw: max_workgroups >= 0");
+  TORCH_CHECK(py_conv3x3_wrw_eligible(dy, x),
+              "conv3x3_wrw: dy or x is not eligible");
+  const Conv3x3WrwPlan p = conv3x3_wrw_plan_of(dy, x, max_workgroups);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dy.device().index());
+  // the layout the stock weight gradient of a channels_last model has:
+  // memory [N][3][3][C], which is what the kernel's columns (3r+s)*C + c are
+  auto dw = at::empty({p.n, p.c, 3, 3}, dy.options(),
+                      at::MemoryFormat::ChannelsLast);
+  auto part =
+      at::empty({p.splits, p.n, 9 * p.c}, dy.options().dtype(at::kFloat));
+  launch_conv3x3_wrw(p, dy.data_ptr(), x.data_ptr(), part.data_ptr<float>(),
+                     dw.data_ptr(), bn_stream(dy));
+  return dw;
+}
+
+py::dict py_conv3x3_wrw_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
+                             int64_t n, int64_t max_workgroups) {
+  const Conv3x3WrwPlan p = conv3x3_wrw_plan(batch, h, w, c, n, max_workgroups);
+  py::dict d;
+  d["eligible"] = p.eligible;
+  d["native"] = p.native;
+  d["threads"] = kConvThreads;
+  d["bn"] = p.bn;
+  d["bk"] = p.bk;
+  d["ntiles_n"] = p.ntiles_n;
+  d["ntiles_k"] = p.ntiles_k;
+  d["images"] = p.images;
+  d["group_rows"] = p.group_rows;
+  d["hr"] = p.hr;
+  d["chunks_per_image"] = p.chunks_per_image;
+  d["chunks"] = p.chunks;
+  d["strip_dy"] = p.strip_dy;
+  d["strip_x"] = p.strip_x;
+  d["splits"] = p.splits;
+  d["grid"] = p.grid;
+  d["chunks_per_split"] = p.chunks_per_split;
+  d["lds_bytes"] = p.lds_bytes;
+  d["lds_budget"] = kConvLdsBytes;
+  d["partial_floats"] = p.partial_floats;
+  return d;
+}
+
+// Test seam: the tensor row b*H + h, or -1 for a zero row, that row t of a
+// group is to the kernel.
+int py_conv3x3_wrw_row(int64_t batch, int64_t h, int64_t w, int64_t c,
+                       int64_t n, int64_t max_workgroups, int group, int t) {
+  const Conv3x3WrwPlan p = conv3x3_wrw_plan(batch, h, w, c, n, max_workgroups);
+  TORCH_CHECK(p.eligible, "conv3x3_wrw_row: shape is not eligible");
+  return conv3x3_wrw_row(p, group, t);
+}
+
 // Test seam: the kernel's walk replayed on the host.  Entry [wg, i] holds
 // (n0, k0, split, row0, row1) of the i-th chunk of workgroup wg: the corner
 // of its tile of dW, the plane of the partials it writes and the rows it
@@ -1727,6 +1799,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("k"), py::arg("n"), py::arg("max_workgroups") = 0,
         "Test seam: [grid, chunks_per_split, 5] int64, (n0, k0, split, row0, "
         "row1) of every row chunk each workgroup visits (-1: none).");
+  m.def("conv3x3_wrw", &cgx::py_conv3x3_wrw, py::arg("dy"), py::arg("x"),
+        py::arg("max_workgroups") = 0,
+        "Weight gradient of conv2d(x, weight, padding=1) for a 3x3 / stride 1 "
+        "convolution on channels_last bf16 tensors, as a channels_last "
+        "[N, C, 3, 3]; accumulated in fp32 in a fixed order and rounded "
+        "once.");
+  m.def("conv3x3_wrw_eligible", &cgx::py_conv3x3_wrw_eligible, py::arg("dy"),
+        py::arg("x"), "True where conv3x3_wrw takes (dy, x).");
+  m.def("conv3x3_wrw_plan", &cgx::py_conv3x3_wrw_plan, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("c"), py::arg("n"),
+        py::arg("max_workgroups") = 0,
+        "The launch geometry of conv3x3_wrw, and `native`: whether the model "
+        "uses it for this problem.");
+  m.def("conv3x3_wrw_row", &cgx::py_conv3x3_wrw_row, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("c"), py::arg("n"),
+        py::arg("max_workgroups"), py::arg("group"), py::arg("t"),
+        "Test seam: the tensor row b*H + h that row t of a group of images "
+        "is, or -1 for a zero row.");
   m.def("bn_act2_backward", &cgx::py_bn_act2_backward,
         "Backward of bn_act2_forward: (dy, x3, xd, mean3, invstd3, weight3, "
         "meand, invstdd, weightd, mask) -> (dx3, dxd, dgamma3, dbeta3, "

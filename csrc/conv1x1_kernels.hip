@@ -35,16 +35,15 @@
 #include "bn_moments.h"
 #include "check.h"
 #include "conv1x1_plan.h"
+#include "wrw_image.h"
 
 namespace cgx {
 namespace {
 
 constexpr int kT = kConvThreads;
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // Where 16-byte chunk q of row n of a [rows][KC] bf16 image sits in LDS.  A
@@ -53,11 +52,6 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 template <int KC>
 __device__ inline int w_slot(int n, int q) {
   return n * (KC / 8) + (q ^ (KC == 64 ? (n >> 1) & 7 : n & 15));
-}
-
-// Row of a 32x32 accumulator tile that register i of lane half h holds.
-__device__ inline int acc_row(int i, int h) {
-  return (i & 3) + 8 * (i >> 2) + 4 * h;
 }
 
 // Two accumulators -> two bf16 (round to nearest even, quiet NaN), a in the
@@ -699,15 +693,7 @@ void launch_gemm(const Conv1x1Plan& p, hipStream_t stream, Args... args) {
 // replaced by zeros.  Each workgroup stores its fp32 tile to its split's
 // plane of `part`; conv1x1_wrw_finalize sums the planes in a fixed order.
 
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-
-template <int C>
-__device__ inline int wrw_cell(int r, int u) {
-  const int lin = r * (C / 32) + u;
-  const int swz = C == 64 ? (r >> 1) & 1 : r & 3;
-  return 256 * (lin >> 2) + 64 * ((lin & 3) ^ swz);
-}
+// wrw_cell and wrw_operand: wrw_image.h, shared with conv3x3_kernels.hip.
 
 // The chunk's rows r0 .. r0+63 of channels c0 .. c0+C of src[R, width]: thread
 // tid's C/32 vectors.
@@ -733,18 +719,6 @@ __device__ inline void wrw_store(char* img, const uint4 (&v)[C / 32], int tid) {
     *reinterpret_cast<uint4*>(img + wrw_cell<C>(row, q >> 2) + 16 * (q & 3)) =
         v[i];
   }
-}
-
-// The operand of one 16-row step from a lane's base address: rows +0 .. +3 in
-// elements 0 .. 3, rows +4 .. +7 in elements 4 .. 7.
-template <int C>
-__device__ inline bf16x8 wrw_operand(char* img, int base, int s) {
-  char* a = img + base + s * 16 * 2 * C;
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (lds_bf16x4*)a);
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (lds_bf16x4*)(a + 4 * 2 * C));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
 template <int BN, int BK>
@@ -1132,22 +1106,23 @@ void launch_wrw_ring(const Conv1x1WrwRingPlan& p, const void* dy,
   CGX_HIP_CHECK(hipGetLastError());
 }
 
-// the sum of the planes that either kernel wrote
-void launch_wrw_finalize(const Conv1x1WrwPlan& p, const float* part, void* dw,
-                         hipStream_t stream) {
+}  // namespace
+
+// the sum of the planes that a weight-gradient kernel wrote
+void launch_wrw_finalize(const float* part, void* dw, int splits,
+                         int64_t elements, hipStream_t stream) {
+  TORCH_CHECK(elements % (8 * kT) == 0, "wrw_finalize: whole workgroups");
   // lanes per vector: as many as the splits give work to, until the grid
   // has four waves for every SIMD
-  const int64_t vecs = (int64_t)p.n * p.k / 8;
+  const int64_t vecs = elements / 8;
   int g = 1;
-  while (g < 16 && 2 * g <= p.splits && vecs * g < 4 * kConvCus * kT) g *= 2;
+  while (g < 16 && 2 * g <= splits && vecs * g < 4 * kConvCus * kT) g *= 2;
   hipLaunchKernelGGL(conv1x1_wrw_finalize, dim3((unsigned)(vecs * g / kT)),
                      dim3(kT), 0, stream,
                      reinterpret_cast<const float4*>(part),
-                     static_cast<uint4*>(dw), p.splits, vecs, g);
+                     static_cast<uint4*>(dw), splits, vecs, g);
   CGX_HIP_CHECK(hipGetLastError());
 }
-
-}  // namespace
 
 void launch_conv1x1_wrw(const Conv1x1WrwPlan& p, const void* dy, const void* x,
                         float* part, void* dw, hipStream_t stream) {
@@ -1156,7 +1131,7 @@ void launch_conv1x1_wrw(const Conv1x1WrwPlan& p, const void* dy, const void* x,
   else if (p.bn == 128) launch_wrw_bn<128>(p, dy, x, part, stream);
   else launch_wrw_bn<256>(p, dy, x, part, stream);
   CGX_HIP_CHECK(hipGetLastError());
-  launch_wrw_finalize(p, part, dw, stream);
+  launch_wrw_finalize(part, dw, p.splits, (int64_t)p.n * p.k, stream);
 }
 
 void launch_conv1x1_wrw_ring(const Conv1x1WrwRingPlan& p, const void* dy,
@@ -1164,7 +1139,7 @@ void launch_conv1x1_wrw_ring(const Conv1x1WrwRingPlan& p, const void* dy,
                              hipStream_t stream) {
   TORCH_CHECK(p.eligible, "conv1x1_wrw_ring: shape is not eligible");
   launch_wrw_ring<kWrwRingTile, kWrwRingTile>(p, dy, x, part, stream);
-  launch_wrw_finalize(p, part, dw, stream);
+  launch_wrw_finalize(part, dw, p.splits, (int64_t)p.n * p.k, stream);
 }
 
 void launch_conv1x1_bwd_data(const Conv1x1Plan& p, const void* dy,

@@ -249,6 +249,13 @@ void launch_conv1x1_wrw_ring(const Conv1x1WrwRingPlan& p, const void* dy,
                              const void* x, float* part, void* dw,
                              hipStream_t stream);
 
+// dw[e] = bf16(part[0][e] + ... + part[splits - 1][e]) for `elements`
+// elements, a multiple of 2048, summed in a fixed order
+// (conv1x1_wrw_finalize): what launch_conv1x1_wrw ends with, for the other
+// weight gradients that write such planes.
+void launch_wrw_finalize(const float* part, void* dw, int splits,
+                         int64_t elements, hipStream_t stream);
+
 // y[R, N] bf16 and part[splits, pstride] fp32 from x[R, K] and w[N, K] bf16;
 // every pointer 16-byte aligned.
 void launch_conv1x1_stats(const Conv1x1Plan& p, const void* x, const void* w,

@@ -1,0 +1,125 @@
+// Launch geometry of the 3x3 weight gradient: see conv3x3_plan.h.
+#include "conv3x3_plan.h"
+
+#include <algorithm>
+
+namespace cgx {
+namespace {
+
+// The problems (batch, H, W, C, N) at which conv3x3_wrw plus the finalize
+// beat MIOpen's fill + igemm + cast in every run of an alternating
+// measurement on MI355X: the slowest native run faster than the fastest stock
+// run (benchmarks/conv3x3_wrw_shapes.py, table in benchmarks/RESULTS.md).
+// Measured at these sizes only, so only they go native.  256->256 at 14x14
+// and 512->512 at 7x7 of ResNet-50 at batch 256 did not meet the rule (their
+// medians are within 5% of the stock path's either way) and stay stock.
+struct Measured3x3 {
+  int batch, h, w, c, n;
+};
+constexpr Measured3x3 kNativeWrw3x3[] = {
+    {256, 56, 56, 64, 64},
+    {256, 28, 28, 128, 128},
+};
+
+bool pow2_in(int64_t v, int64_t lo, int64_t hi) {
+  return v >= lo && v <= hi && (v & (v - 1)) == 0;
+}
+
+int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+unsigned magic_of(int d) {
+  return (unsigned)(((1u << kConv3x3MagicShift) + d - 1) / d);
+}
+
+int strip_dy_of(int rows, int pitch) { return round_up(rows * pitch, 16); }
+// every index that a position below the rounded dY strip reaches with the
+// last tap, offset 2*pitch + 2, in whole lines of the image
+int strip_x_of(int rows, int pitch) {
+  return round_up(strip_dy_of(rows, pitch) + 2 * pitch + 2, 4);
+}
+
+// whether chunks of `rows` rows pass through the staging registers
+bool fits(int rows, int pitch, int bn, int bk) {
+  return strip_dy_of(rows, pitch) * (bn / 8) <= kConv3x3DyVecs * kConvThreads &&
+         strip_x_of(rows, pitch) * (bk / 8) <= kConv3x3XVecs * kConvThreads;
+}
+
+// The chunks for at most `limit` rows each: as many whole images as fit, or
+// one image in the fewest chunks, of equal length but the last.
+void set_chunks(Conv3x3WrwPlan& p, int limit) {
+  const int whole = std::min((limit + 1) / (p.h + 1), p.batch);
+  if (whole >= 2) {
+    p.images = whole;
+    p.group_rows = whole * (p.h + 1) - 1;
+    p.chunks_per_image = 1;
+    p.hr = p.group_rows;
+  } else {
+    p.images = 1;
+    p.group_rows = p.h;
+    p.chunks_per_image = (p.h + limit - 1) / limit;
+    p.hr = (p.h + p.chunks_per_image - 1) / p.chunks_per_image;
+  }
+  const int groups = (p.batch + p.images - 1) / p.images;
+  p.chunks = groups * p.chunks_per_image;
+}
+
+}  // namespace
+
+Conv3x3WrwPlan conv3x3_wrw_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
+                                int64_t n, int64_t max_workgroups) {
+  Conv3x3WrwPlan p;
+  // 64 x 64 is the one tile: nine accumulator tiles per wave, 144 registers
+  p.bn = p.bk = 64;
+  p.eligible = pow2_in(c, 64, 512) && pow2_in(n, 64, 512) && batch >= 1 &&
+               h >= 1 && w >= 1 && batch <= kBnMaxRows && h <= kBnMaxRows &&
+               w <= kBnMaxRows && batch * h * w <= kBnMaxRows &&
+               fits(1, (int)w + 1, p.bn, p.bk);
+  if (!p.eligible) return p;
+  p.batch = (int)batch, p.h = (int)h, p.w = (int)w, p.c = (int)c, p.n = (int)n;
+  for (const Measured3x3& m : kNativeWrw3x3)
+    p.native |= m.batch == batch && m.h == h && m.w == w && m.c == c && m.n == n;
+  p.pitch = p.w + 1;
+  p.ntiles_n = p.n / p.bn;
+  p.ntiles_k = p.c / p.bk;
+  const int tiles = p.ntiles_n * p.ntiles_k;
+
+  // One workgroup per CU: the strips take most of LDS.  No more splits than
+  // keep the partials, 4*N*9C bytes per split written and read back once,
+  // within the bytes the workgroups read of the operands: 2*R*(N + C) once
+  // per tile of the other operand's channels.
+  const int64_t rows = batch * h * w;
+  const int64_t operand_bytes =
+      2 * rows * (n * p.ntiles_k + c * p.ntiles_n);
+  const int64_t by_bytes = std::max<int64_t>(1, operand_bytes / (72 * n * c));
+  int64_t splits = std::min<int64_t>(by_bytes, std::max(1, kConvCus / tiles));
+  if (max_workgroups > 0)
+    splits = std::min(splits, std::max<int64_t>(
+                                  1, std::min<int64_t>(max_workgroups, 1 << 20) /
+                                         tiles));
+
+  // The longest chunk that fits.  With 64-wide tiles the bytes rule above
+  // comes to one split per 1152 pixels (72*N*C bytes of partials against
+  // 2*R*2*N*C/64 of operands) and a chunk holds at most 384 positions, so
+  // every split has chunks without shortening them; the clamp below is for
+  // the rounding at problems of a single chunk.
+  int limit = 1;
+  while (fits(limit + 1, p.pitch, p.bn, p.bk) &&
+         limit + 1 <= (int)std::min<int64_t>(batch * (h + 1), 1 << 10))
+    limit++;
+  set_chunks(p, limit);
+  splits = std::min<int64_t>(splits, p.chunks);
+  if (splits > 8) splits -= splits % 8;  // conv3x3_wrw_split
+  p.splits = (int)splits;
+  p.grid = tiles * p.splits;
+  p.chunks_per_split = (p.chunks + p.splits - 1) / p.splits;
+
+  p.strip_dy = strip_dy_of(p.hr, p.pitch);
+  p.strip_x = strip_x_of(p.hr, p.pitch);
+  p.lds_bytes = (p.strip_dy * p.bn + p.strip_x * p.bk) * 2;
+  p.partial_floats = (int64_t)p.splits * p.n * 9 * p.c;
+  p.magic_pitch = magic_of(p.pitch);
+  p.magic_h1 = magic_of(p.h + 1);
+  return p;
+}
+
+}  // namespace cgx

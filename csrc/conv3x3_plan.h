@@ -1,0 +1,103 @@
+// Launch geometry of the weight gradient of a 3x3 / stride 1 / padding 1
+// convolution (conv3x3_wrw in conv3x3_kernels.hip).
+//
+// Pure host arithmetic, like conv1x1_plan.h.  dW[n, c, r, s] = sum over b, h, w
+// of dY[b, n, h, w] * X[b, c, h+r-1, w+s-1] on channels_last bf16 tensors is
+// the GEMM dW[N, 9C] with column (3r+s)*C + c, contracted over the pixels.  A
+// 256-thread workgroup owns a bn x bk tile of channels (its four waves 2 x 2)
+// with all nine taps, and one of `splits` slices of the pixels.
+//
+// A chunk is `hr` rows of pitch P = W+1.  dY is staged in LDS as the strip of
+// positions j = row*P + w with the pad w = W zero, X as rows -1 .. hr at index
+// i = (row+1)*P + wx + 1 with column 0 zero, so that tap (r, s) pairs position
+// j with index j + r*P + s: the taps share both strips and differ by an LDS
+// offset.  The rows of a chunk are rows of a `group`: `images` whole images
+// stacked with one zero row between them, group_rows = images*(H+1) - 1 rows.
+// With images == 1 a group is one image, cut into chunks_per_image chunks of
+// hr rows, the last one maybe short.  Where several images fit one chunk
+// (7x7 and smaller) images > 1 and the group is the chunk: the rounding of a strip
+// to 16 positions and the per-chunk barriers are paid once for all of them.
+//
+// Each workgroup writes its fp32 tile to part[split][N][9C]; the finalize of
+// the 1x1 weight gradient sums the planes in a fixed order.
+#pragma once
+
+#include <cstdint>
+
+#include "conv1x1_plan.h"
+
+namespace cgx {
+
+// A thread stages a chunk through registers, at most this many 16-byte
+// vectors of dY and of X: strips of 384 and 512 positions at a 64-channel
+// tile, 112 KiB of the 160 KiB of LDS.  With more of them the kernel spills
+// to scratch; so this, not LDS, is what bounds hr and the image width
+// (W <= 166, where one row is a chunk).
+constexpr int kConv3x3DyVecs = 12;
+constexpr int kConv3x3XVecs = 16;
+// row = (j * magic) >> kConv3x3MagicShift is j / d for the j < 2^10 and
+// d < 2^9 that occur, magic = ceil(2^20 / d)
+constexpr int kConv3x3MagicShift = 20;
+
+struct Conv3x3WrwPlan {
+  int batch = 0, h = 0, w = 0, c = 0, n = 0;
+  bool eligible = false;
+  bool native = false;  // measured faster than MIOpen's fill + igemm + cast
+  int bn = 0, bk = 0;   // the workgroup's tile of dW's channels
+  int ntiles_n = 0, ntiles_k = 0;
+  int pitch = 0;       // W + 1
+  int images = 0;      // images of a group
+  int group_rows = 0;  // images * (H + 1) - 1
+  int hr = 0;          // rows of a chunk
+  int chunks_per_image = 0;  // chunks of a group
+  int chunks = 0;            // groups * chunks_per_image
+  int strip_dy = 0, strip_x = 0;  // positions of the two LDS strips
+  int splits = 0;  // workgroups per channel tile
+  int grid = 0;    // ntiles_n * ntiles_k * splits
+  int chunks_per_split = 0;  // longest walk
+  int lds_bytes = 0;
+  int64_t partial_floats = 0;  // splits * N * 9C
+  unsigned magic_pitch = 0, magic_h1 = 0;  // for j / pitch and t / (H + 1)
+};
+
+// C and N powers of two in [64, 512], batch*H*W within kBnMaxRows, and W
+// narrow enough for one row to be a chunk.  `max_workgroups` > 0 caps the
+// grid.
+Conv3x3WrwPlan conv3x3_wrw_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
+                                int64_t n, int64_t max_workgroups = 0);
+
+// Workgroup -> (tile, split) as conv1x1_wrw_tile / _split: the workgroups of
+// one slice 8 apart, on one XCD, wherever the splits divide by 8.  Split s
+// walks chunks s, s + splits, ...
+__host__ __device__ inline int conv3x3_wrw_tile(const Conv3x3WrwPlan& p,
+                                                int wg) {
+  const int tiles = p.ntiles_n * p.ntiles_k;
+  return p.splits % 8 == 0 ? (wg / 8) % tiles : wg % tiles;
+}
+__host__ __device__ inline int conv3x3_wrw_split(const Conv3x3WrwPlan& p,
+                                                 int wg) {
+  const int tiles = p.ntiles_n * p.ntiles_k;
+  return p.splits % 8 == 0 ? (wg / 8 / tiles) * 8 + wg % 8 : wg / tiles;
+}
+
+// Row t of group `group` as a row b*H + h of the tensors, or -1 where it is
+// a zero row: before or after the group, between two images, past the batch.
+__host__ __device__ inline int conv3x3_wrw_row(const Conv3x3WrwPlan& p,
+                                               int group, int t) {
+  if (t < 0 || t >= p.group_rows) return -1;
+  int image = 0, h = t;
+  if (p.images > 1) {
+    image = (int)(((unsigned)t * p.magic_h1) >> kConv3x3MagicShift);
+    h = t - image * (p.h + 1);
+  }
+  const int b = group * p.images + image;
+  return h < p.h && b < p.batch ? b * p.h + h : -1;
+}
+
+// dw[N, 3, 3, C] bf16 (the memory of a channels_last [N, C, 3, 3]) from
+// dy[B, H, W, N] and x[B, H, W, C] bf16 through part[splits, N, 9C] fp32,
+// which needs no initialisation; every pointer 16-byte aligned.
+void launch_conv3x3_wrw(const Conv3x3WrwPlan& p, const void* dy, const void* x,
+                        float* part, void* dw, hipStream_t stream);
+
+}  // namespace cgx

@@ -53,6 +53,12 @@ switches and the tiled one are off wherever the forward one is, the tiled
 input gradient also wherever ``CGX_NATIVE_CONV1X1_BWD`` is, and the ring
 wherever ``CGX_NATIVE_CONV1X1_WRW`` is.
 
+``conv3x3(conv, x)`` is ``conv(x)`` for the 3x3 / stride 1 / padding 1
+convolution of a bottleneck.  Its weight gradient has a native implicit GEMM
+(``_C.conv3x3_wrw``, csrc/conv3x3_kernels.hip) with the fixed summation order
+of the 1x1 one; ``CGX_NATIVE_CONV3X3_WRW`` switches it like the others and
+depends on none of them.
+
 ``CGX_FUSED_BN=0`` switches all native paths off.
 """
 
@@ -414,6 +420,75 @@ def conv_bn_act_fork(conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d,
     (``_Conv1x1``).  Where that does not apply ``skip`` is ``x``."""
     y, part, skip = _conv(conv, bn, x, fork=True)
     return bn_act(bn, y, None, relu, part=part), skip
+
+
+class _Conv3x3(torch.autograd.Function):
+    """``conv2d(x, weight, padding=1)`` whose weight gradient comes from the
+    native implicit GEMM (``_C.conv3x3_wrw``) where it takes the gradient that
+    arrives, else from the stock backward; the input gradient is the stock
+    one."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
+    def forward(ctx, x, weight):
+        ctx.save_for_backward(x, weight)
+        return F.conv2d(x, weight, padding=1)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        need_dx, need_dw = ctx.needs_input_grad
+        dx = dw = None
+        if need_dw and _C.conv3x3_wrw_eligible(dy, x):
+            dw, need_dw = _C.conv3x3_wrw(dy, x), False
+        if need_dx or need_dw:
+            dx, dw_stock, _ = torch.ops.aten.convolution_backward(
+                dy, x, weight, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1,
+                (need_dx, need_dw, False))
+            dw = dw_stock if need_dw else dw
+        return dx, dw
+
+
+def native_conv3x3_wrw_mode() -> str:
+    """``CGX_NATIVE_CONV3X3_WRW``: "0" off, "all" every eligible problem, else
+    ("1", the default) the problems its plan has measured faster.  Off where
+    ``CGX_FUSED_BN`` is; the 1x1 switches do not reach it."""
+    if not fused_bn_enabled():
+        return "0"
+    return os.environ.get("CGX_NATIVE_CONV3X3_WRW", "1")
+
+
+def conv3x3(conv: torch.nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+    """``conv(x)``.  For a bias-free 3x3 / stride 1 / padding 1 convolution of
+    a channels_last bf16 CUDA activation whose weight gradient the native
+    kernel is to compute (``native_conv3x3_wrw_mode``) it goes through
+    ``_Conv3x3``; in every other case it is the module call itself."""
+    mode = native_conv3x3_wrw_mode()
+    if mode == "0" or not torch.is_grad_enabled():
+        return conv(x)
+    if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == (3, 3)
+            and conv.stride == (1, 1) and conv.padding == (1, 1)
+            and conv.dilation == (1, 1) and conv.groups == 1
+            and conv.bias is None and conv.padding_mode == "zeros"
+            and conv.weight.requires_grad):
+        return conv(x)
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16
+            and _C.bn_eligible(x)):
+        return conv(x)
+    w = conv.weight
+    # under bf16 autocast the fp32 weight reaches the convolution as bf16
+    autocast = (torch.is_autocast_enabled("cuda")
+                and torch.get_autocast_dtype("cuda") == torch.bfloat16)
+    if not (w.device == x.device and w.shape[1] == x.shape[1]
+            and (w.dtype == torch.bfloat16
+                 or (autocast and w.dtype == torch.float32))):
+        return conv(x)
+    plan = _C.conv3x3_wrw_plan(x.shape[0], x.shape[2], x.shape[3], x.shape[1],
+                               w.shape[0])
+    if not (plan["eligible"] and (plan["native"] or mode == "all")):
+        return conv(x)
+    return _Conv3x3.apply(x, w)
 
 
 def _pool_is_3x3_s2_p1(pool) -> bool:
