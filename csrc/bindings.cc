@@ -1365,6 +1365,118 @@ int py_conv3x3_wrw_row(int64_t batch, int64_t h, int64_t w, int64_t c,
   return conv3x3_wrw_row(p, group, t);
 }
 
+// ---- 3x3 convolution forward with statistics --------------------------------
+
+Conv3x3FwdPlan conv3x3_fwd_plan_of(const at::Tensor& x, const at::Tensor& w,
+                                   int64_t max_workgroups = 0) {
+  return conv3x3_fwd_plan(x.size(0), x.size(2), x.size(3), x.size(1),
+                          w.size(0), max_workgroups);
+}
+
+// x as the BatchNorm kernels take it and a dense, 16-byte aligned bf16
+// [N, C, 3, 3] weight in channels_last, whose memory is [N][3][3][C].
+bool py_conv3x3_fwd_eligible(const at::Tensor& x, const at::Tensor& w) {
+  return bn_tensor_ok(x) && w.is_cuda() && w.device() == x.device() &&
+         w.scalar_type() == at::kBFloat16 && w.dim() == 4 && w.size(2) == 3 &&
+         w.size(3) == 3 && w.size(1) == x.size(1) &&
+         w.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+         reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0 &&
+         conv3x3_fwd_plan_of(x, w).eligible;
+}
+
+// conv2d(x, weight, padding=1) -> (y, part); part holds the BatchNorm
+// partials of y in the layout of conv1x1_stats
+std::tuple<at::Tensor, at::Tensor> py_conv3x3_stats(const at::Tensor& x,
+                                                    const at::Tensor& weight,
+                                                    int64_t max_workgroups) {
+  TORCH_CHECK(max_workgroups >= 0, "conv3x3_stats: max_workgroups >= 0");
+  TORCH_CHECK(py_conv3x3_fwd_eligible(x, weight),
+              "conv3x3_stats: input or weight is not eligible");
+  const Conv3x3FwdPlan p = conv3x3_fwd_plan_of(x, weight, max_workgroups);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device().index());
+  auto y = at::empty({x.size(0), p.n, x.size(2), x.size(3)}, x.options(),
+                     at::MemoryFormat::ChannelsLast);
+  auto part = at::empty({p.splits, p.pstride}, x.options().dtype(at::kFloat));
+  launch_conv3x3_stats(p, x.data_ptr(), weight.data_ptr(), y.data_ptr(),
+                       part.data_ptr<float>(), bn_stream(x));
+  return {y, part};
+}
+
+py::dict py_conv3x3_fwd_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
+                             int64_t n, int64_t max_workgroups) {
+  const Conv3x3FwdPlan p = conv3x3_fwd_plan(batch, h, w, c, n, max_workgroups);
+  py::dict d;
+  d["eligible"] = p.eligible;
+  d["native"] = p.native;
+  d["threads"] = kConvThreads;
+  d["rows"] = p.rows;
+  d["bn"] = p.bn;
+  d["ntiles"] = p.ntiles;
+  d["tile_rows"] = p.tile_rows;
+  d["kc"] = p.kc;
+  d["nchunks"] = p.nchunks;
+  d["resident"] = p.resident;
+  d["row_tiles"] = p.row_tiles;
+  d["strip_rows"] = p.strip_rows;
+  d["xvecs"] = p.xvecs;
+  d["splits"] = p.splits;
+  d["grid"] = p.grid;
+  d["tiles_per_split"] = p.tiles_per_split;
+  d["run"] = p.run;
+  d["lds_bytes"] = p.lds_bytes;
+  d["lds_budget"] = kConvLdsBytes;
+  d["pstride"] = p.pstride;
+  d["partial_floats"] = p.partial_floats;
+  return d;
+}
+
+// Test seam: the kernel's walk replayed on the host.  Entry [wg, i] holds
+// (n0, split, row0, row1) of the i-th tile of workgroup wg, -1 once it has
+// run out of tiles.
+at::Tensor py_conv3x3_fwd_walk(int64_t batch, int64_t h, int64_t w, int64_t c,
+                               int64_t n, int64_t max_workgroups) {
+  const Conv3x3FwdPlan p = conv3x3_fwd_plan(batch, h, w, c, n, max_workgroups);
+  TORCH_CHECK(p.eligible, "conv3x3_fwd_walk: shape is not eligible");
+  auto out = at::full({p.grid, p.tiles_per_split, 4}, -1,
+                      at::TensorOptions().dtype(at::kLong));
+  int64_t* o = out.data_ptr<int64_t>();
+  for (int wg = 0; wg < p.grid; wg++) {
+    const int split = conv3x3_fwd_split(p, wg);
+    int i = 0;
+    for (int t = split; t < p.row_tiles; t += p.splits, i++) {
+      TORCH_CHECK(i < p.tiles_per_split, "conv3x3_fwd_walk: walk too long");
+      int64_t* e = o + ((int64_t)wg * p.tiles_per_split + i) * 4;
+      e[0] = conv3x3_fwd_ntile(p, wg) * p.bn;
+      e[1] = split;
+      e[2] = (int64_t)t * p.tile_rows;
+      e[3] = std::min<int64_t>(e[2] + p.tile_rows, p.rows);
+    }
+  }
+  return out;
+}
+
+// Test seam: entry [row, tap] is the pixel whose channels the kernel
+// multiplies with tap 3r + s of the weight for output pixel `row`, read
+// through the strip of the row's tile, or -1 where it clears the operand.
+at::Tensor py_conv3x3_fwd_taps(int64_t batch, int64_t h, int64_t w, int64_t c,
+                               int64_t n) {
+  const Conv3x3FwdPlan p = conv3x3_fwd_plan(batch, h, w, c, n);
+  TORCH_CHECK(p.eligible, "conv3x3_fwd_taps: shape is not eligible");
+  auto out = at::empty({p.rows, 9}, at::TensorOptions().dtype(at::kLong));
+  int64_t* o = out.data_ptr<int64_t>();
+  for (int row = 0; row < p.rows; row++) {
+    const unsigned valid = conv3x3_fwd_taps(p, row);
+    const int t = row / p.tile_rows, m = row % p.tile_rows;
+    for (int tap = 0; tap < 9; tap++) {
+      const int i = conv3x3_fwd_strip_index(p, m, tap);
+      TORCH_CHECK(i >= 0 && i < p.strip_rows, "conv3x3_fwd_taps: off the strip");
+      o[row * 9 + tap] =
+          (valid >> tap) & 1 ? conv3x3_fwd_strip_row(p, t, i) : -1;
+    }
+  }
+  return out;
+}
+
 // Test seam: the kernel's walk replayed on the host.  Entry [wg, i] holds
 // (n0, k0, split, row0, row1) of the i-th chunk of workgroup wg: the corner
 // of its tile of dW, the plane of the partials it writes and the rows it
@@ -1817,6 +1929,31 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("max_workgroups"), py::arg("group"), py::arg("t"),
         "Test seam: the tensor row b*H + h that row t of a group of images "
         "is, or -1 for a zero row.");
+  m.def("conv3x3_stats", &cgx::py_conv3x3_stats, py::arg("x"),
+        py::arg("weight"), py::arg("max_workgroups") = 0,
+        "conv2d(x, weight, padding=1) of a 3x3 / stride 1 convolution by the "
+        "native implicit GEMM -> (y, part): part are the BatchNorm partials "
+        "of y, in the layout of conv1x1_stats, for bn_act_forward.  "
+        "max_workgroups > 0 caps the grid.");
+  m.def("conv3x3_fwd_eligible", &cgx::py_conv3x3_fwd_eligible, py::arg("x"),
+        py::arg("weight"),
+        "True where conv3x3_stats takes (x, weight): CUDA, bf16, dense "
+        "channels_last and 16-byte aligned, C and N powers of two in "
+        "[64, 512].");
+  m.def("conv3x3_fwd_plan", &cgx::py_conv3x3_fwd_plan, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("c"), py::arg("n"),
+        py::arg("max_workgroups") = 0,
+        "The launch geometry of conv3x3_stats, and `native`: whether the "
+        "model uses it for this problem.");
+  m.def("conv3x3_fwd_walk", &cgx::py_conv3x3_fwd_walk, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("c"), py::arg("n"),
+        py::arg("max_workgroups") = 0,
+        "Test seam: [grid, tiles_per_split, 4] int64, (n0, split, row0, row1) "
+        "of every tile a workgroup of conv3x3_stats walks (-1: none).");
+  m.def("conv3x3_fwd_taps", &cgx::py_conv3x3_fwd_taps, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("c"), py::arg("n"),
+        "Test seam: [rows, 9] int64, the pixel each tap of each output pixel "
+        "reads through its tile's strip, -1 where the operand is cleared.");
   m.def("bn_act2_backward", &cgx::py_bn_act2_backward,
         "Backward of bn_act2_forward: (dy, x3, xd, mean3, invstd3, weight3, "
         "meand, invstdd, weightd, mask) -> (dx3, dxd, dgamma3, dbeta3, "

@@ -1,5 +1,7 @@
-// Weight gradient of a 3x3 / stride 1 / padding 1 convolution on
-// channels_last bf16 tensors as an implicit GEMM.  Geometry: conv3x3_plan.h.
+// The 3x3 / stride 1 / padding 1 convolution on channels_last bf16 tensors as
+// implicit GEMMs: the weight gradient (conv3x3_wrw, first) and the forward
+// that also produces BatchNorm partials (conv3x3_stats, below it, with its
+// own description).  Geometry: conv3x3_plan.h.
 //
 // dW[n][(3r+s)*C + c] = sum over pixels of dY[b, h, w, n] * X[b, h+r-1, w+s-1, c].
 // Both operands have the contracted index slow, so both MFMA operands are
@@ -46,6 +48,7 @@
 // once: no atomics, the same bits every run.
 #include <hip/hip_runtime.h>
 
+#include "bn_moments.h"
 #include "check.h"
 #include "conv3x3_plan.h"
 #include "wrw_image.h"
@@ -218,7 +221,346 @@ void launch_wrw3x3(const Conv3x3WrwPlan& p, const void* dy, const void* x,
   CGX_HIP_CHECK(hipGetLastError());
 }
 
+// ---- forward with BatchNorm partials ------------------------------------------
+//
+// y = conv2d(x, w, padding 1) and the partials of y for the BatchNorm that
+// follows, as conv1x1_stats produces them.  Geometry: Conv3x3FwdPlan.
+//
+//   A   the strip of a tile, [64*xvecs pixels][32 channels], 64 bytes a pixel.
+//       Lane (c, h) of a wave reads for tap (r, s) the 16 bytes of pixel
+//       m + c + r*W + s, channels 8*(2k + h) .. +7 of 16-deep step k, and
+//       clears them where the pixel's bit of conv3x3_fwd_taps is not set: a
+//       select, so whatever the strip holds there never reaches a product
+//   B   a weight chunk, [9 taps][64 channels][32 channels of X], the row of
+//       (tap, n) at index 64*tap + n
+//   C   a wave owns 64 rows x 64 channels, four accumulator tiles, so each
+//       ds_read_b128 of A and each of B feeds two MFMAs; per 16-deep step and
+//       tap that is four reads for four MFMAs, against ten for nine in
+//       conv3x3_wrw
+//
+// Both images have 64-byte rows, fwd_slot: the 16 lanes that one pass of a
+// ds_read_b128 serves read 16 consecutive rows j at one q, which start
+// anywhere because the taps shift them.  Row j lies in the 64-byte column
+// j & 3 of a 256-byte bank row and the XOR with (j >> 2) & 3 gives the four
+// rows of a column four different 16-byte slots; j & 15 takes all 16 values
+// on 16 consecutive rows, so the pass is conflict-free at every start.  The
+// copies write whole rows from consecutive lanes.
+//
+// A stage is one 32-channel chunk of one tile: 72 MFMAs a wave.  A thread
+// loads its share of the next stage, at most nine vectors of the strip and
+// nine of the weight, into registers before the MFMAs of this one and writes
+// them to the other buffers after them, so one barrier a stage orders both
+// (gemm_walk_tiled).  The accumulators take 64 registers and the staged
+// vectors 72: the kernel is far from the register bound of conv3x3_wrw.  Every
+// accumulator is one chain over (chunk, tap, step) in ascending order, and
+// the moments merge in a fixed tree: the same bits every run.
+
+constexpr int kFwdWVecs = kConv3x3FwdWBytes / 16;  // of a weight chunk
+constexpr int kFwdWShare = kFwdWVecs / kT;         // ... and of a thread
+static_assert(kFwdWVecs % kT == 0 && kConv3x3FwdBn == 64 &&
+              kConv3x3FwdKc == 32 && kConv3x3FwdTileRows == 4 * 64);
+
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// 16-byte vector q of row j of an image with 64-byte rows
+__device__ inline int fwd_slot(int j, int q) {
+  return j * 4 + (q ^ ((j >> 2) & 3));
+}
+
+// as pack_bf16 of conv1x1_kernels.hip: what bf16_bits gives, a in the low half
+__device__ inline unsigned fwd_pack_bf16(float a, float b) {
+  const f32x2 f = {a, b};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
+}
+
+// vector q of channels n0 .. n0+63 of chunk kc of the weight's row (tap, n)
+__device__ inline const uint4* fwd_w_src(const uint4* __restrict__ w,
+                                         const Conv3x3FwdPlan& p, int n0,
+                                         int kc, int idx) {
+  const int q = idx & 3, row = idx >> 2, tap = row >> 6, n = row & 63;
+  return w + ((int64_t)((n0 + n) * 9 + tap) * p.c + kc * kConv3x3FwdKc) / 8 + q;
+}
+
+// A thread's share of one stage in registers (plain vectors: a uint4 member
+// would keep the whole struct in scratch).
+template <bool RES>
+struct FwdStage {
+  u32x4 wv[RES ? 1 : kFwdWShare], xv[kConv3x3FwdXVecs];
+  __device__ __forceinline__ void load(const uint4* __restrict__ x,
+                                       const uint4* __restrict__ w,
+                                       const Conv3x3FwdPlan& p, int n0,
+                                       int tile, int kc, int tid) {
+    if (!RES) {
+#pragma unroll
+      for (int i = 0; i < kFwdWShare; i++)
+        wv[i] = *reinterpret_cast<const u32x4*>(
+            fwd_w_src(w, p, n0, kc, tid + i * kT));
+    }
+#pragma unroll
+    for (int i = 0; i < kConv3x3FwdXVecs; i++)
+      if (i < p.xvecs) {  // uniform
+        const int idx = tid + i * kT;
+        const int64_t r = conv3x3_fwd_strip_row(p, tile, idx >> 2);
+        xv[i] = *reinterpret_cast<const u32x4*>(
+            x + (r * p.c + kc * kConv3x3FwdKc) / 8 + (idx & 3));
+      }
+  }
+  __device__ __forceinline__ void store(uint4* wb, uint4* xb,
+                                        const Conv3x3FwdPlan& p,
+                                        int tid) const {
+    if (!RES) {
+#pragma unroll
+      for (int i = 0; i < kFwdWShare; i++) {
+        const int idx = tid + i * kT;
+        *reinterpret_cast<u32x4*>(wb + fwd_slot(idx >> 2, idx & 3)) = wv[i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < kConv3x3FwdXVecs; i++)
+      if (i < p.xvecs) {
+        const int idx = tid + i * kT;
+        *reinterpret_cast<u32x4*>(xb + fwd_slot(idx >> 2, idx & 3)) = xv[i];
+      }
+  }
+};
+
+template <bool RES>
+__global__ __launch_bounds__(kT) void conv3x3_stats(
+    const uint4* __restrict__ x, const uint4* __restrict__ w,
+    uint4* __restrict__ y, float* __restrict__ part, Conv3x3FwdPlan p) {
+  extern __shared__ uint4 lds[];
+  constexpr int BN = kConv3x3FwdBn, M = kConv3x3FwdTileRows;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int c = lane & 31, h = lane >> 5;
+  const int ntile = conv3x3_fwd_ntile(p, blockIdx.x);
+  const int split = conv3x3_fwd_split(p, blockIdx.x);
+  const int n0 = ntile * BN, nvec = p.n / 8;
+  const int xbuf = p.xvecs * kT;  // vectors of a strip buffer
+  uint4* wimg = lds;              // two weight chunks
+  uint4* ximg = lds + 2 * kFwdWVecs;  // two strips
+  uint4* stage = ximg + 2 * xbuf + wave * 256;  // [32 rows][64 channels]
+  unsigned* stage32 = reinterpret_cast<unsigned*>(stage);
+
+  if (RES) {  // the two chunks are the two buffers, for good
+    for (int idx = tid; idx < 2 * kFwdWVecs; idx += kT) {
+      const int kc = idx / kFwdWVecs, v = idx % kFwdWVecs;
+      wimg[kc * kFwdWVecs + fwd_slot(v >> 2, v & 3)] =
+          *fwd_w_src(w, p, n0, kc, v);
+    }
+  }
+
+  FwdStage<RES> st;
+  int tile = split, kc = 0, buf = 0;  // split < row_tiles
+  st.load(x, w, p, n0, tile, 0, tid);
+  st.store(wimg, ximg, p, tid);
+
+  // The lane's moments are those of v - pivot, pivot the first value the lane
+  // pushes: a difference of two bf16 values, exact in fp32.  The roundings of
+  // a run then scale with the spread of the values, not with their mean
+  // (outputs near 100 with unit spread lose two digits of M2 otherwise), and
+  // the pivot returns where the runs merge.
+  Moments<2> mo;
+  float pivot[2] = {0.f, 0.f};
+  auto push = [&](const float (&v)[2]) __attribute__((always_inline)) {
+    float d[2];
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+      pivot[j] = mo.n == 0.f ? v[j] : pivot[j];
+      d[j] = v[j] - pivot[j];
+    }
+    mo.push(d);
+  };
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int s = 0; s < 2; s++)
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+      for (int e = 0; e < 16; e++) acc[s][j][e] = 0.f;
+  unsigned valid[2] = {0, 0};
+
+  while (tile < p.row_tiles) {
+    // The next stage, of this tile or the first of the next, is loaded before
+    // the MFMAs of this one.  All waves walk the same stages, so each
+    // reaches every barrier.
+    int nkc = kc + 1, ntl = tile;
+    if (nkc == p.nchunks) nkc = 0, ntl = tile + p.splits;
+    const bool more = ntl < p.row_tiles;
+    if (more) st.load(x, w, p, n0, ntl, nkc, tid);
+    // buffer `buf` is written, and the other one, read a stage ago, is free
+    __syncthreads();
+    if (kc == 0) {
+#pragma unroll
+      for (int s = 0; s < 2; s++)
+        valid[s] = conv3x3_fwd_taps(p, tile * M + wave * 64 + s * 32 + c);
+    }
+    const uint4* wl = wimg + buf * kFwdWVecs;
+    const uint4* xl = ximg + buf * xbuf;
+    uint4 av[2][2], bv[2][2];  // the operands of this step and the next
+    auto read = [&](int u) {
+      const int tap = u >> 1, q = 2 * (u & 1) + h;
+#pragma unroll
+      for (int s = 0; s < 2; s++) {
+        const int j = conv3x3_fwd_strip_index(p, wave * 64 + s * 32 + c, tap);
+        const uint4 v = xl[fwd_slot(j, q)];
+        const unsigned m = 0u - ((valid[s] >> tap) & 1u);
+        av[u & 1][s] = make_uint4(v.x & m, v.y & m, v.z & m, v.w & m);
+      }
+#pragma unroll
+      for (int j = 0; j < 2; j++)
+        bv[u & 1][j] = wl[fwd_slot(tap * 64 + j * 32 + c, q)];
+    };
+    read(0);
+#pragma unroll
+    for (int u = 0; u < 18; u++) {
+      if (u + 1 < 18) read(u + 1);
+#pragma unroll
+      for (int s = 0; s < 2; s++)
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+          acc[s][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              __builtin_bit_cast(bf16x8, av[u & 1][s]),
+              __builtin_bit_cast(bf16x8, bv[u & 1][j]), acc[s][j], 0, 0, 0);
+    }
+    // nothing that waits for the loads above may move up among the MFMAs
+    __builtin_amdgcn_sched_barrier(0);
+    buf ^= 1;
+    if (more) st.store(wimg + buf * kFwdWVecs, ximg + buf * xbuf, p, tid);
+
+    if (nkc == 0) {
+      // The tile is complete: round, push, store, as conv1x1_stats does
+      // (stats_body in conv1x1_kernels.hip), one 32-row sub-tile at a time.
+#pragma unroll
+      for (int s = 0; s < 2; s++) {
+        const int r0 = tile * M + wave * 64 + s * 32;
+        const int live = p.rows - r0 < 32 ? p.rows - r0 : 32;  // may be <= 0
+        unsigned pk[2][8];
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+          for (int e = 0; e < 8; e++)
+            pk[j][e] = fwd_pack_bf16(acc[s][j][2 * e], acc[s][j][2 * e + 1]);
+        // the moments of the rounded values: what bn_apply will normalise
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+          float lo[2], hi[2];
+#pragma unroll
+          for (int j = 0; j < 2; j++) {
+            lo[j] = __uint_as_float(pk[j][e] << 16);
+            hi[j] = __uint_as_float(pk[j][e] & 0xffff0000u);
+          }
+          if (acc_row(2 * e, h) < live) push(lo);
+          if (acc_row(2 * e + 1, h) < live) push(hi);
+        }
+        // Lanes c and c^1 trade words so that the even lane writes channels
+        // (c, c+1) of row 2e and the odd one channels (c-1, c) of row 2e+1;
+        // odd rows swap their 64-byte halves.
+        const int odd = c & 1;
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+          for (int e = 0; e < 8; e++) {
+            const unsigned own = pk[j][e];
+            // quad_perm [1, 0, 3, 2]
+            const unsigned other = (unsigned)__builtin_amdgcn_update_dpp(
+                0, (int)own, 0xB1, 0xf, 0xf, false);
+            const unsigned word = odd ? (other >> 16) | (own & 0xffff0000u)
+                                      : (own & 0xffffu) | (other << 16);
+            const int row = acc_row(2 * e, h) + odd;
+            stage32[row * 32 + ((j * 16 + (c >> 1)) ^ ((row & 1) << 4))] = word;
+          }
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+          const int idx = u * 64 + lane, row = idx >> 3, q = idx & 7;
+          const uint4 v = stage[row * 8 + (q ^ ((row & 1) << 2))];
+          if (row < live) y[(int64_t)(r0 + row) * nvec + n0 / 8 + q] = v;
+        }
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+          for (int e = 0; e < 16; e++) acc[s][j][e] = 0.f;
+      }
+    }
+    kc = nkc, tile = ntl;
+  }
+
+  // The eight runs of every channel -> one partial, as a tree.  A merge
+  // keeps the pivot of its first run (of the second where the first is
+  // empty) and moves the other mean there: the difference of the pivots is
+  // exact and the sum is of the size of the spread.  The pivot is added once,
+  // at the end.
+  __syncthreads();
+  float* sc = reinterpret_cast<float*>(lds);
+  const int run = wave * 2 + h;
+#pragma unroll
+  for (int j = 0; j < 2; j++) {
+    sc[run * BN + j * 32 + c] = mo.mean[j];
+    sc[(8 + run) * BN + j * 32 + c] = mo.m2[j];
+    sc[(16 + run) * BN + j * 32 + c] = pivot[j];
+  }
+  if (c == 0) sc[24 * BN + run] = mo.n;
+  __syncthreads();
+  if (tid < BN) {
+    Moments<1> m[8];
+    float pv[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+      m[r].n = sc[24 * BN + r];
+      m[r].mean[0] = sc[r * BN + tid];
+      m[r].m2[0] = sc[(8 + r) * BN + tid];
+      pv[r] = sc[(16 + r) * BN + tid];
+    }
+#pragma unroll
+    for (int step = 1; step < 8; step *= 2)
+#pragma unroll
+      for (int r = 0; r < 8; r += 2 * step) {
+        pv[r] = m[r].n > 0.f ? pv[r] : pv[r + step];
+        const float mb[1] = {m[r + step].n > 0.f
+                                 ? (pv[r + step] - pv[r]) + m[r + step].mean[0]
+                                 : 0.f};
+        m[r].merge(m[r + step].n, mb, m[r + step].m2);
+      }
+    float* row = part + (int64_t)split * p.pstride;
+    row[n0 + tid] = pv[0] + m[0].mean[0];
+    row[p.n + n0 + tid] = m[0].m2[0];
+    if (tid == 0) row[2 * p.n + ntile] = m[0].n;
+  }
+}
+
+template <bool RES>
+void launch_fwd3x3(const Conv3x3FwdPlan& p, const void* x, const void* w,
+                   void* y, float* part, hipStream_t stream) {
+  static const hipError_t attr = hipFuncSetAttribute(
+      reinterpret_cast<const void*>(&conv3x3_stats<RES>),
+      hipFuncAttributeMaxDynamicSharedMemorySize, kConvLdsBytes);
+  CGX_HIP_CHECK(attr);
+  hipLaunchKernelGGL((conv3x3_stats<RES>), dim3(p.grid), dim3(kT), p.lds_bytes,
+                     stream, static_cast<const uint4*>(x),
+                     static_cast<const uint4*>(w), static_cast<uint4*>(y),
+                     part, p);
+  CGX_HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace
+
+void launch_conv3x3_stats(const Conv3x3FwdPlan& p, const void* x, const void* w,
+                          void* y, float* part, hipStream_t stream) {
+  TORCH_CHECK(p.eligible, "conv3x3_stats: shape is not eligible");
+  TORCH_CHECK(p.bn == kConv3x3FwdBn && p.kc == kConv3x3FwdKc &&
+                  p.xvecs <= kConv3x3FwdXVecs &&
+                  p.strip_rows <= 64 * p.xvecs && p.splits <= p.row_tiles &&
+                  p.resident == (p.nchunks == 2) &&
+                  p.lds_bytes <= kConvLdsBytes,
+              "conv3x3_stats: plan and kernel disagree");
+  if (p.resident) launch_fwd3x3<true>(p, x, w, y, part, stream);
+  else launch_fwd3x3<false>(p, x, w, y, part, stream);
+}
 
 void launch_conv3x3_wrw(const Conv3x3WrwPlan& p, const void* dy, const void* x,
                         float* part, void* dw, hipStream_t stream) {

@@ -1,4 +1,4 @@
-// Launch geometry of the 3x3 weight gradient: see conv3x3_plan.h.
+// Launch geometry of the 3x3 weight gradient and forward: see conv3x3_plan.h.
 #include "conv3x3_plan.h"
 
 #include <algorithm>
@@ -19,6 +19,17 @@ struct Measured3x3 {
 constexpr Measured3x3 kNativeWrw3x3[] = {
     {256, 56, 56, 64, 64},
     {256, 28, 28, 128, 128},
+};
+
+// The same rule for conv3x3_stats followed by bn_act_forward with its partials
+// against MIOpen's forward followed by bn_act_forward with a statistics pass
+// (benchmarks/conv3x3_fwd_shapes.py).  All four bottleneck problems of
+// ResNet-50 at batch 256 met it.
+constexpr Measured3x3 kNativeFwd3x3[] = {
+    {256, 56, 56, 64, 64},
+    {256, 28, 28, 128, 128},
+    {256, 14, 14, 256, 256},
+    {256, 7, 7, 512, 512},
 };
 
 bool pow2_in(int64_t v, int64_t lo, int64_t hi) {
@@ -119,6 +130,47 @@ Conv3x3WrwPlan conv3x3_wrw_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
   p.partial_floats = (int64_t)p.splits * p.n * 9 * p.c;
   p.magic_pitch = magic_of(p.pitch);
   p.magic_h1 = magic_of(p.h + 1);
+  return p;
+}
+
+Conv3x3FwdPlan conv3x3_fwd_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
+                                int64_t n, int64_t max_workgroups) {
+  Conv3x3FwdPlan p;
+  p.bn = kConv3x3FwdBn;
+  p.tile_rows = kConv3x3FwdTileRows;
+  p.kc = kConv3x3FwdKc;
+  const int64_t strip = p.tile_rows + 2 * w + 2;
+  p.eligible = pow2_in(c, 64, 512) && pow2_in(n, 64, 512) && batch >= 1 &&
+               h >= 1 && w >= 1 && batch <= kBnMaxRows && h <= kBnMaxRows &&
+               w <= kBnMaxRows && batch * h * w <= kBnMaxRows &&
+               batch * h * w >= 2 && strip <= 64 * kConv3x3FwdXVecs;
+  if (!p.eligible) return p;
+  p.batch = (int)batch, p.h = (int)h, p.w = (int)w, p.c = (int)c, p.n = (int)n;
+  p.rows = (int)(batch * h * w);
+  for (const Measured3x3& m : kNativeFwd3x3)
+    p.native |= m.batch == batch && m.h == h && m.w == w && m.c == c && m.n == n;
+  p.ntiles = p.n / p.bn;
+  p.nchunks = p.c / p.kc;
+  p.resident = p.nchunks == 2;
+  p.row_tiles = (p.rows + p.tile_rows - 1) / p.tile_rows;
+  p.strip_rows = (int)strip;
+  p.xvecs = (p.strip_rows + 63) / 64;
+
+  // one workgroup per CU: the buffers take most of LDS
+  int64_t splits = std::min<int64_t>(p.row_tiles, std::max(1, kConvCus / p.ntiles));
+  if (max_workgroups > 0)
+    splits = std::min(splits, std::max<int64_t>(
+                                  1, std::min<int64_t>(max_workgroups, 1 << 20) /
+                                         p.ntiles));
+  if (splits > 8) splits -= splits % 8;  // conv3x3_fwd_split
+  p.splits = (int)splits;
+  p.grid = p.ntiles * p.splits;
+  p.tiles_per_split = (p.row_tiles + p.splits - 1) / p.splits;
+  p.run = 32 * p.tiles_per_split;
+  p.lds_bytes = 2 * kConv3x3FwdWBytes + 2 * p.xvecs * 64 * p.kc * 2 +
+                kConvStageBytes;
+  p.pstride = 2 * p.n + p.ntiles;
+  p.partial_floats = (int64_t)p.splits * p.pstride;
   return p;
 }
 

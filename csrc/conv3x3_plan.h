@@ -1,5 +1,6 @@
 // Launch geometry of the weight gradient of a 3x3 / stride 1 / padding 1
-// convolution (conv3x3_wrw in conv3x3_kernels.hip).
+// convolution (conv3x3_wrw in conv3x3_kernels.hip) and, further down, of its
+// forward with BatchNorm partials (conv3x3_stats).
 //
 // Pure host arithmetic, like conv1x1_plan.h.  dW[n, c, r, s] = sum over b, h, w
 // of dY[b, n, h, w] * X[b, c, h+r-1, w+s-1] on channels_last bf16 tensors is
@@ -99,5 +100,99 @@ __host__ __device__ inline int conv3x3_wrw_row(const Conv3x3WrwPlan& p,
 // which needs no initialisation; every pointer 16-byte aligned.
 void launch_conv3x3_wrw(const Conv3x3WrwPlan& p, const void* dy, const void* x,
                         float* part, void* dw, hipStream_t stream);
+
+// ---- forward with BatchNorm partials (conv3x3_stats) -------------------------
+//
+// Y[R, N] = sum over the nine taps t of X_t[R, C] * W_t[N, C]^T, R = B*H*W the
+// pixels in memory order.  The rows of the GEMM are the pixels themselves, not
+// positions of a padded strip: a 256-thread workgroup owns 64 output channels
+// and walks tiles of 256 consecutive pixels, whatever images they belong to
+// (at 7x7 a tile holds more than five images), wave w rows 64*w .. 64*w+63 as
+// two 32-row sub-tiles.  The strip of a tile is the pixels 256*t - (W+1) ..
+// 256*t + 256 + W of one 32-channel chunk of X in LDS, so tap (r, s) of tile
+// row m is strip index m + r*W + s: the nine taps share the strip and differ
+// by an LDS offset.  The strip has no zero pads.  A neighbour that lies in
+// another image row, another image or outside the tensor is a row of the
+// strip like any other (outside the tensor: the nearest pixel inside), and
+// the lane sets its operand to zero in registers: conv3x3_fwd_taps gives the
+// pixel's nine validity bits.  So no tile row is a pad, every row below R is
+// stored and pushed into the moments, and the count of a workgroup is the
+// number of pixels it walked.
+//
+// The weight goes through LDS in [tap][64][32] chunks, one per chunk of the
+// strip, both double-buffered.  At C == 64 the two chunks are the two buffers
+// and stay (`resident`).  The grid, the walk, the moments and the partials are
+// those of conv1x1_tiled_plan: `splits` persistent workgroups per channel
+// tile, each writing one row [mean(N) | M2(N) | count(ntiles)].
+constexpr int kConv3x3FwdTileRows = 256;
+constexpr int kConv3x3FwdBn = 64;
+constexpr int kConv3x3FwdKc = 32;
+// bytes of one weight chunk, [9][64][32] bf16
+constexpr int kConv3x3FwdWBytes = 9 * kConv3x3FwdBn * kConv3x3FwdKc * 2;
+// a thread's share of a strip, in 16-byte vectors: 64 strip rows each
+constexpr int kConv3x3FwdXVecs = 9;
+
+struct Conv3x3FwdPlan {
+  int batch = 0, h = 0, w = 0, c = 0, n = 0;
+  int rows = 0;  // R
+  bool eligible = false;
+  bool native = false;  // measured faster than MIOpen + bn_stats
+  int bn = 0;           // channels per workgroup
+  int ntiles = 0;       // workgroups across N
+  int tile_rows = 0;
+  int kc = 0, nchunks = 0;  // channel chunk and C / kc
+  bool resident = false;    // C == 64: the weight is staged once
+  int row_tiles = 0;        // ceil(R / tile_rows)
+  int strip_rows = 0;       // tile_rows + 2W + 2
+  int xvecs = 0;            // ceil(strip_rows / 64); a buffer holds 64 * xvecs
+  int splits = 0;           // persistent workgroups per channel tile
+  int grid = 0;             // ntiles * splits
+  int tiles_per_split = 0;  // longest walk
+  int run = 0;              // per-lane run length: 32 * tiles_per_split
+  int lds_bytes = 0;
+  int pstride = 0;             // floats per partial row: 2*N + ntiles
+  int64_t partial_floats = 0;  // splits * pstride
+};
+
+// C and N powers of two in [64, 512], 2 <= B*H*W <= kBnMaxRows, and W up to
+// 159, where the two strip buffers fill what LDS the weight leaves.
+// `max_workgroups` > 0 caps the grid.
+Conv3x3FwdPlan conv3x3_fwd_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
+                                int64_t n, int64_t max_workgroups = 0);
+
+// Workgroup -> (channel tile, split) as conv1x1_tiled_ntile / _split; split s
+// walks row tiles s, s + splits, ...
+__host__ __device__ inline int conv3x3_fwd_ntile(const Conv3x3FwdPlan& p,
+                                                 int wg) {
+  return p.splits % 8 == 0 ? (wg / 8) % p.ntiles : wg % p.ntiles;
+}
+__host__ __device__ inline int conv3x3_fwd_split(const Conv3x3FwdPlan& p,
+                                                 int wg) {
+  return p.splits % 8 == 0 ? (wg / 8 / p.ntiles) * 8 + wg % 8 : wg / p.ntiles;
+}
+// The pixel that index i of tile t's strip holds.
+__host__ __device__ inline int conv3x3_fwd_strip_row(const Conv3x3FwdPlan& p,
+                                                     int t, int i) {
+  const int r = t * kConv3x3FwdTileRows - (p.w + 1) + i;
+  return r < 0 ? 0 : r < p.rows ? r : p.rows - 1;
+}
+// The strip index that tap = 3r + s of tile row m reads.
+__host__ __device__ inline int conv3x3_fwd_strip_index(const Conv3x3FwdPlan& p,
+                                                       int m, int tap) {
+  return m + (tap / 3) * p.w + tap % 3;
+}
+// Bit 3r + s is set where pixel `row` has a neighbour (h+r-1, w+s-1) in its
+// own image.
+__host__ __device__ inline unsigned conv3x3_fwd_taps(const Conv3x3FwdPlan& p,
+                                                     int row) {
+  const int line = row / p.w, w = row - line * p.w, h = line % p.h;
+  const unsigned cols = (w > 0 ? 1u : 0u) | 2u | (w + 1 < p.w ? 4u : 0u);
+  return (h > 0 ? cols : 0u) | cols << 3 | (h + 1 < p.h ? cols << 6 : 0u);
+}
+
+// y[B, H, W, N] bf16 and part[splits, pstride] fp32 from x[B, H, W, C] and
+// w[N, 3, 3, C] bf16; every pointer 16-byte aligned.
+void launch_conv3x3_stats(const Conv3x3FwdPlan& p, const void* x, const void* w,
+                          void* y, float* part, hipStream_t stream);
 
 }  // namespace cgx

@@ -11,7 +11,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from ..ops.fused_bn import (bn_act, bn_act_pool, conv3x3, conv_bn_act,
+from ..ops.fused_bn import (bn_act, bn_act_pool, conv3x3_bn_act, conv_bn_act,
                             conv_bn_act_fork)
 
 
@@ -38,7 +38,8 @@ class Bottleneck(nn.Module):
         # (benchmarks/RESULTS.md); the skip path leaves from conv1, whose
         # backward-data GEMM then adds that path's gradient in its epilogue
         out, identity = conv_bn_act_fork(self.conv1, self.bn1, x)
-        out = bn_act(self.bn2, conv3x3(self.conv2, out))
+        # ... and so does the 3x3 one where its native forward runs
+        out = conv3x3_bn_act(self.conv2, self.bn2, out)
         if self.downsample is not None:
             # the downsample BatchNorm is the second operand of bn3's sweeps:
             # its output and its gradient never go through memory

@@ -57,7 +57,10 @@ wherever ``CGX_NATIVE_CONV1X1_WRW`` is.
 convolution of a bottleneck.  Its weight gradient has a native implicit GEMM
 (``_C.conv3x3_wrw``, csrc/conv3x3_kernels.hip) with the fixed summation order
 of the 1x1 one; ``CGX_NATIVE_CONV3X3_WRW`` switches it like the others and
-depends on none of them.
+depends on none of them.  ``conv3x3_bn_act(conv, bn, x)`` is
+``bn_act(bn, conv3x3(conv, x))`` with a native forward as well
+(``_C.conv3x3_stats``), which hands ``bn`` its statistics as the 1x1 forward
+does; ``CGX_NATIVE_CONV3X3`` switches it, on its own.
 
 ``CGX_FUSED_BN=0`` switches all native paths off.
 """
@@ -423,59 +426,78 @@ def conv_bn_act_fork(conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d,
 
 
 class _Conv3x3(torch.autograd.Function):
-    """``conv2d(x, weight, padding=1)`` whose weight gradient comes from the
+    """``(y, part) = f(x, weight)``: ``conv2d(x, weight, padding=1)``, by the
+    native implicit GEMM with the BatchNorm partials of ``y``
+    (``_C.conv3x3_stats``) where ``native_fwd`` says so, else stock with
+    ``part`` None.  With ``native_wrw`` the weight gradient comes from the
     native implicit GEMM (``_C.conv3x3_wrw``) where it takes the gradient that
     arrives, else from the stock backward; the input gradient is the stock
     one."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
-    def forward(ctx, x, weight):
+    def forward(ctx, x, weight, native_fwd, native_wrw):
         ctx.save_for_backward(x, weight)
-        return F.conv2d(x, weight, padding=1)
+        ctx.native_wrw = native_wrw
+        if native_fwd:
+            y, part = _C.conv3x3_stats(x, weight)
+            ctx.mark_non_differentiable(part)
+            return y, part
+        return F.conv2d(x, weight, padding=1), None
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
-    def backward(ctx, dy):
+    def backward(ctx, dy, _dpart):
         x, weight = ctx.saved_tensors
-        need_dx, need_dw = ctx.needs_input_grad
+        need_dx, need_dw = ctx.needs_input_grad[:2]
         dx = dw = None
-        if need_dw and _C.conv3x3_wrw_eligible(dy, x):
+        if need_dw and ctx.native_wrw and _C.conv3x3_wrw_eligible(dy, x):
             dw, need_dw = _C.conv3x3_wrw(dy, x), False
         if need_dx or need_dw:
             dx, dw_stock, _ = torch.ops.aten.convolution_backward(
                 dy, x, weight, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1,
                 (need_dx, need_dw, False))
             dw = dw_stock if need_dw else dw
-        return dx, dw
+        return dx, dw, None, None
 
 
 def native_conv3x3_wrw_mode() -> str:
     """``CGX_NATIVE_CONV3X3_WRW``: "0" off, "all" every eligible problem, else
     ("1", the default) the problems its plan has measured faster.  Off where
-    ``CGX_FUSED_BN`` is; the 1x1 switches do not reach it."""
+    ``CGX_FUSED_BN`` is; the 1x1 switches and ``CGX_NATIVE_CONV3X3`` do not
+    reach it."""
     if not fused_bn_enabled():
         return "0"
     return os.environ.get("CGX_NATIVE_CONV3X3_WRW", "1")
 
 
-def conv3x3(conv: torch.nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
-    """``conv(x)``.  For a bias-free 3x3 / stride 1 / padding 1 convolution of
-    a channels_last bf16 CUDA activation whose weight gradient the native
-    kernel is to compute (``native_conv3x3_wrw_mode``) it goes through
-    ``_Conv3x3``; in every other case it is the module call itself."""
-    mode = native_conv3x3_wrw_mode()
-    if mode == "0" or not torch.is_grad_enabled():
-        return conv(x)
+def native_conv3x3_mode() -> str:
+    """``CGX_NATIVE_CONV3X3``, the switch of the forward with statistics, with
+    the values of ``CGX_NATIVE_CONV3X3_WRW`` and as independent."""
+    if not fused_bn_enabled():
+        return "0"
+    return os.environ.get("CGX_NATIVE_CONV3X3", "1")
+
+
+def _conv3x3(conv, x, bn=None):
+    """``(conv(x), part)``.  For a bias-free 3x3 / stride 1 / padding 1
+    convolution of a channels_last bf16 CUDA activation it goes through
+    ``_Conv3x3`` where the native forward (only with a training ``bn`` to
+    take its partials) or the native weight gradient is to run, each by its
+    own switch and its plan's table; in every other case it is the module
+    call itself and ``part`` is None."""
+    fwd_mode = native_conv3x3_mode() if bn is not None else "0"
+    wrw_mode = native_conv3x3_wrw_mode() if torch.is_grad_enabled() else "0"
+    if fwd_mode == "0" and wrw_mode == "0":
+        return conv(x), None
     if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == (3, 3)
             and conv.stride == (1, 1) and conv.padding == (1, 1)
             and conv.dilation == (1, 1) and conv.groups == 1
-            and conv.bias is None and conv.padding_mode == "zeros"
-            and conv.weight.requires_grad):
-        return conv(x)
+            and conv.bias is None and conv.padding_mode == "zeros"):
+        return conv(x), None
     if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16
             and _C.bn_eligible(x)):
-        return conv(x)
+        return conv(x), None
     w = conv.weight
     # under bf16 autocast the fp32 weight reaches the convolution as bf16
     autocast = (torch.is_autocast_enabled("cuda")
@@ -483,12 +505,37 @@ def conv3x3(conv: torch.nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
     if not (w.device == x.device and w.shape[1] == x.shape[1]
             and (w.dtype == torch.bfloat16
                  or (autocast and w.dtype == torch.float32))):
-        return conv(x)
-    plan = _C.conv3x3_wrw_plan(x.shape[0], x.shape[2], x.shape[3], x.shape[1],
-                               w.shape[0])
-    if not (plan["eligible"] and (plan["native"] or mode == "all")):
-        return conv(x)
-    return _Conv3x3.apply(x, w)
+        return conv(x), None
+    shape = (x.shape[0], x.shape[2], x.shape[3], x.shape[1], w.shape[0])
+
+    def takes(mode, plan):
+        return mode != "0" and plan["eligible"] and (plan["native"]
+                                                     or mode == "all")
+
+    # the cast of a weight keeps its strides: the kernel wants [N][3][3][C]
+    fwd = (takes(fwd_mode, _C.conv3x3_fwd_plan(*shape))
+           and _native(bn, x, None)
+           and w.is_contiguous(memory_format=torch.channels_last)
+           and (w.dtype != torch.bfloat16 or _C.conv3x3_fwd_eligible(x, w)))
+    wrw = w.requires_grad and takes(wrw_mode, _C.conv3x3_wrw_plan(*shape))
+    if not (fwd or wrw):
+        return conv(x), None
+    return _Conv3x3.apply(x, w, fwd, wrw)
+
+
+def conv3x3(conv: torch.nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+    """``conv(x)``, through ``_Conv3x3`` where the native weight gradient is
+    to compute the gradient of its weight (``native_conv3x3_wrw_mode``)."""
+    return _conv3x3(conv, x)[0]
+
+
+def conv3x3_bn_act(conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d,
+                   x: torch.Tensor, relu: bool = True) -> torch.Tensor:
+    """``relu(bn(conv(x)))`` for the 3x3 convolution of a bottleneck: where
+    the native forward runs (``native_conv3x3_mode``), ``bn`` takes its
+    statistics from the partials that come with the output."""
+    y, part = _conv3x3(conv, x, bn)
+    return bn_act(bn, y, None, relu, part=part)
 
 
 def _pool_is_3x3_s2_p1(pool) -> bool:
