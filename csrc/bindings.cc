@@ -1402,9 +1402,7 @@ std::tuple<at::Tensor, at::Tensor> py_conv3x3_stats(const at::Tensor& x,
   return {y, part};
 }
 
-py::dict py_conv3x3_fwd_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
-                             int64_t n, int64_t max_workgroups) {
-  const Conv3x3FwdPlan p = conv3x3_fwd_plan(batch, h, w, c, n, max_workgroups);
+py::dict conv3x3_fwd_plan_dict(const Conv3x3FwdPlan& p) {
   py::dict d;
   d["eligible"] = p.eligible;
   d["native"] = p.native;
@@ -1428,6 +1426,55 @@ py::dict py_conv3x3_fwd_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
   d["pstride"] = p.pstride;
   d["partial_floats"] = p.partial_floats;
   return d;
+}
+
+py::dict py_conv3x3_fwd_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
+                             int64_t n, int64_t max_workgroups) {
+  return conv3x3_fwd_plan_dict(
+      conv3x3_fwd_plan(batch, h, w, c, n, max_workgroups));
+}
+
+// ---- 3x3 convolution input gradient -------------------------------------------
+
+Conv3x3FwdPlan conv3x3_bwd_plan_of(const at::Tensor& dy, const at::Tensor& w,
+                                   int64_t max_workgroups = 0) {
+  return conv3x3_bwd_plan(dy.size(0), dy.size(2), dy.size(3), w.size(1),
+                          w.size(0), max_workgroups);
+}
+
+// dy as the BatchNorm kernels take it and the weight as the forward takes it,
+// [N, C, 3, 3] with the N of dy.
+bool py_conv3x3_bwd_eligible(const at::Tensor& dy, const at::Tensor& w) {
+  return bn_tensor_ok(dy) && w.is_cuda() && w.device() == dy.device() &&
+         w.scalar_type() == at::kBFloat16 && w.dim() == 4 && w.size(2) == 3 &&
+         w.size(3) == 3 && w.size(0) == dy.size(1) &&
+         w.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+         reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0 &&
+         conv3x3_bwd_plan_of(dy, w).eligible;
+}
+
+// the input gradient of conv2d(x, weight, padding=1) from the gradient dy of
+// its output
+at::Tensor py_conv3x3_bwd_data(const at::Tensor& dy, const at::Tensor& weight,
+                               int64_t max_workgroups) {
+  TORCH_CHECK(max_workgroups >= 0, "conv3x3_bwd_data: max_workgroups >= 0");
+  TORCH_CHECK(py_conv3x3_bwd_eligible(dy, weight),
+              "conv3x3_bwd_data: dy or weight is not eligible");
+  const Conv3x3FwdPlan p = conv3x3_bwd_plan_of(dy, weight, max_workgroups);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dy.device().index());
+  auto dx = at::empty({dy.size(0), weight.size(1), dy.size(2), dy.size(3)},
+                      dy.options(), at::MemoryFormat::ChannelsLast);
+  launch_conv3x3_bwd_data(p, dy.data_ptr(), weight.data_ptr(), dx.data_ptr(),
+                          bn_stream(dy));
+  return dx;
+}
+
+// The forward's keys: `nchunks` and `resident` are those of N, the contraction
+// depth here, and `ntiles` those of C.
+py::dict py_conv3x3_bwd_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
+                             int64_t n, int64_t max_workgroups) {
+  return conv3x3_fwd_plan_dict(
+      conv3x3_bwd_plan(batch, h, w, c, n, max_workgroups));
 }
 
 // Test seam: the kernel's walk replayed on the host.  Entry [wg, i] holds
@@ -1945,6 +1992,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("max_workgroups") = 0,
         "The launch geometry of conv3x3_stats, and `native`: whether the "
         "model uses it for this problem.");
+  m.def("conv3x3_bwd_data", &cgx::py_conv3x3_bwd_data, py::arg("dy"),
+        py::arg("weight"), py::arg("max_workgroups") = 0,
+        "Input gradient of conv2d(x, weight, padding=1) of a 3x3 / stride 1 "
+        "convolution by the native implicit GEMM -> dx, channels_last bf16; "
+        "the weight is the convolution's own [N, C, 3, 3], read transposed.  "
+        "max_workgroups > 0 caps the grid.");
+  m.def("conv3x3_bwd_eligible", &cgx::py_conv3x3_bwd_eligible, py::arg("dy"),
+        py::arg("weight"),
+        "True where conv3x3_bwd_data takes (dy, weight): CUDA, bf16, dense "
+        "channels_last and 16-byte aligned, a [N, C, 3, 3] weight with the N "
+        "of dy, C and N powers of two in [64, 512].");
+  m.def("conv3x3_bwd_plan", &cgx::py_conv3x3_bwd_plan, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("c"), py::arg("n"),
+        py::arg("max_workgroups") = 0,
+        "The launch geometry of conv3x3_bwd_data for dx [batch, c, h, w] from "
+        "dy [batch, n, h, w], with the keys of conv3x3_fwd_plan(batch, h, w, "
+        "n, c), and `native`: whether the model uses it for this problem.");
   m.def("conv3x3_fwd_walk", &cgx::py_conv3x3_fwd_walk, py::arg("batch"),
         py::arg("h"), py::arg("w"), py::arg("c"), py::arg("n"),
         py::arg("max_workgroups") = 0,

@@ -1,7 +1,8 @@
 // The 3x3 / stride 1 / padding 1 convolution on channels_last bf16 tensors as
-// implicit GEMMs: the weight gradient (conv3x3_wrw, first) and the forward
-// that also produces BatchNorm partials (conv3x3_stats, below it, with its
-// own description).  Geometry: conv3x3_plan.h.
+// implicit GEMMs: the weight gradient (conv3x3_wrw, first), the forward that
+// also produces BatchNorm partials (conv3x3_stats, below it) and the input
+// gradient (conv3x3_bwd_data, last), each with its own description.
+// Geometry: conv3x3_plan.h.
 //
 // dW[n][(3r+s)*C + c] = sum over pixels of dY[b, h, w, n] * X[b, h+r-1, w+s-1, c].
 // Both operands have the contracted index slow, so both MFMA operands are
@@ -275,6 +276,44 @@ __device__ inline unsigned fwd_pack_bf16(float a, float b) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
 }
 
+// A wave's 32 x 64 sub-tile, pk[j][e] the packed rows acc_row(2e, h) and
+// acc_row(2e+1, h) of channel 32j + c, through the wave's `stage` to rows
+// r0 .. r0+live-1 (live may be <= 0), channels n0 .. n0+63 of out[., 8*nvec],
+// as 16-byte row vectors.
+__device__ __forceinline__ void fwd_store_subtile(
+    const unsigned (&pk)[2][8], uint4* stage, uint4* __restrict__ out, int r0,
+    int live, int nvec, int n0, int lane) {
+  unsigned* stage32 = reinterpret_cast<unsigned*>(stage);
+  const int c = lane & 31, h = lane >> 5;
+  // Lanes c and c^1 trade words so that the even lane writes channels
+  // (c, c+1) of row 2e and the odd one channels (c-1, c) of row 2e+1;
+  // odd rows swap their 64-byte halves.
+  const int odd = c & 1;
+#pragma unroll
+  for (int j = 0; j < 2; j++)
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+      const unsigned own = pk[j][e];
+      // quad_perm [1, 0, 3, 2]
+      const unsigned other = (unsigned)__builtin_amdgcn_update_dpp(
+          0, (int)own, 0xB1, 0xf, 0xf, false);
+      const unsigned word = odd ? (other >> 16) | (own & 0xffff0000u)
+                                : (own & 0xffffu) | (other << 16);
+      const int row = acc_row(2 * e, h) + odd;
+      stage32[row * 32 + ((j * 16 + (c >> 1)) ^ ((row & 1) << 4))] = word;
+    }
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int u = 0; u < 4; u++) {
+    const int idx = u * 64 + lane, row = idx >> 3, q = idx & 7;
+    const uint4 v = stage[row * 8 + (q ^ ((row & 1) << 2))];
+    if (row < live) out[(int64_t)(r0 + row) * nvec + n0 / 8 + q] = v;
+  }
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+}
+
 // vector q of channels n0 .. n0+63 of chunk kc of the weight's row (tap, n)
 __device__ inline const uint4* fwd_w_src(const uint4* __restrict__ w,
                                          const Conv3x3FwdPlan& p, int n0,
@@ -283,9 +322,25 @@ __device__ inline const uint4* fwd_w_src(const uint4* __restrict__ w,
   return w + ((int64_t)((n0 + n) * 9 + tap) * p.c + kc * kConv3x3FwdKc) / 8 + q;
 }
 
+// The same for conv3x3_bwd_data, whose plan has the roles exchanged (p.c is
+// the N of dY, p.n the C of dX): vector idx of the [9 taps][32 n][64 c] chunk
+// kc of the weight [N][3][3][C], channels c0 .. c0+63 of row (tap, n) ...
+__device__ inline const uint4* bwd_w_src(const uint4* __restrict__ w,
+                                         const Conv3x3FwdPlan& p, int c0,
+                                         int kc, int idx) {
+  const int q = idx & 7, row = idx >> 3, tap = row >> 5, n = row & 31;
+  return w +
+         ((int64_t)((kc * kConv3x3FwdKc + n) * 9 + tap) * p.n + c0) / 8 + q;
+}
+// ... and where it goes: row 32*tap + n of a 64-channel wrw_cell image
+__device__ inline int bwd_w_slot(int idx) {
+  return wrw_cell<64>(idx >> 3, (idx >> 2) & 1) / 16 + (idx & 3);
+}
+
 // A thread's share of one stage in registers (plain vectors: a uint4 member
-// would keep the whole struct in scratch).
-template <bool RES>
+// would keep the whole struct in scratch).  TR: the weight chunk of
+// conv3x3_bwd_data.
+template <bool RES, bool TR = false>
 struct FwdStage {
   u32x4 wv[RES ? 1 : kFwdWShare], xv[kConv3x3FwdXVecs];
   __device__ __forceinline__ void load(const uint4* __restrict__ x,
@@ -296,7 +351,8 @@ struct FwdStage {
 #pragma unroll
       for (int i = 0; i < kFwdWShare; i++)
         wv[i] = *reinterpret_cast<const u32x4*>(
-            fwd_w_src(w, p, n0, kc, tid + i * kT));
+            TR ? bwd_w_src(w, p, n0, kc, tid + i * kT)
+               : fwd_w_src(w, p, n0, kc, tid + i * kT));
     }
 #pragma unroll
     for (int i = 0; i < kConv3x3FwdXVecs; i++)
@@ -314,7 +370,8 @@ struct FwdStage {
 #pragma unroll
       for (int i = 0; i < kFwdWShare; i++) {
         const int idx = tid + i * kT;
-        *reinterpret_cast<u32x4*>(wb + fwd_slot(idx >> 2, idx & 3)) = wv[i];
+        *reinterpret_cast<u32x4*>(
+            wb + (TR ? bwd_w_slot(idx) : fwd_slot(idx >> 2, idx & 3))) = wv[i];
       }
     }
 #pragma unroll
@@ -341,7 +398,6 @@ __global__ __launch_bounds__(kT) void conv3x3_stats(
   uint4* wimg = lds;              // two weight chunks
   uint4* ximg = lds + 2 * kFwdWVecs;  // two strips
   uint4* stage = ximg + 2 * xbuf + wave * 256;  // [32 rows][64 channels]
-  unsigned* stage32 = reinterpret_cast<unsigned*>(stage);
 
   if (RES) {  // the two chunks are the two buffers, for good
     for (int idx = tid; idx < 2 * kFwdWVecs; idx += kT) {
@@ -454,33 +510,7 @@ __global__ __launch_bounds__(kT) void conv3x3_stats(
           if (acc_row(2 * e, h) < live) push(lo);
           if (acc_row(2 * e + 1, h) < live) push(hi);
         }
-        // Lanes c and c^1 trade words so that the even lane writes channels
-        // (c, c+1) of row 2e and the odd one channels (c-1, c) of row 2e+1;
-        // odd rows swap their 64-byte halves.
-        const int odd = c & 1;
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-#pragma unroll
-          for (int e = 0; e < 8; e++) {
-            const unsigned own = pk[j][e];
-            // quad_perm [1, 0, 3, 2]
-            const unsigned other = (unsigned)__builtin_amdgcn_update_dpp(
-                0, (int)own, 0xB1, 0xf, 0xf, false);
-            const unsigned word = odd ? (other >> 16) | (own & 0xffff0000u)
-                                      : (own & 0xffffu) | (other << 16);
-            const int row = acc_row(2 * e, h) + odd;
-            stage32[row * 32 + ((j * 16 + (c >> 1)) ^ ((row & 1) << 4))] = word;
-          }
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          const int idx = u * 64 + lane, row = idx >> 3, q = idx & 7;
-          const uint4 v = stage[row * 8 + (q ^ ((row & 1) << 2))];
-          if (row < live) y[(int64_t)(r0 + row) * nvec + n0 / 8 + q] = v;
-        }
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
+        fwd_store_subtile(pk, stage, y, r0, live, nvec, n0, lane);
 #pragma unroll
         for (int j = 0; j < 2; j++)
 #pragma unroll
@@ -547,7 +577,181 @@ void launch_fwd3x3(const Conv3x3FwdPlan& p, const void* x, const void* w,
   CGX_HIP_CHECK(hipGetLastError());
 }
 
+// ---- input gradient -----------------------------------------------------------
+//
+// dX[b, c, h, w] = sum over n, r, s of dY[b, n, h+1-r, w+1-s] * W[n, c, r, s]:
+// the forward's GEMM with C and N exchanged, dX[R, C] = sum over taps t of
+// dY_t[R, N] * W_{8-t}[N, C].  The plan is a Conv3x3FwdPlan of the exchanged
+// problem (conv3x3_bwd_plan): p.c is the N of dY, p.n the C of dX.
+//
+//   A   the forward's strip, of dY: with r' = 2 - r, s' = 2 - s the factor of
+//       W[., ., r, s] is the neighbour (h+r'-1, w+s'-1), strip tap
+//       t = 3r' + s', cleared by the same bits of conv3x3_fwd_taps (H, W and
+//       the padding are the forward's); the weight's tap is 8 - t
+//   B   the weight stays [N][3][3][C], so the contracted index n is the slow
+//       one of a chunk [9 taps][32 n][64 c]: 36 KiB like the forward's, copied
+//       row by row (128 bytes) into a 64-channel wrw_cell image, row
+//       32*tap + n, and read transposed as in conv1x1_wrw: two
+//       ds_read_b64_tr_b16 per 32-channel tile and 16-deep step, each feeding
+//       two MFMAs like the forward's ds_read_b128
+//   C   as the forward, without moments
+//
+// Bank conflicts of B.  A transposed read takes per 32-lane half the cell
+// (tile j) of the four rows n = 16k + 8h + 4i .. +3 of one tap, i the first or
+// second read: the C == 64 case of conv1x1_wrw, rows 4m .. 4m+3 at a multiple
+// of four, whose cells lie in the four 64-byte columns (2*(r & 1) + j) ^
+// ((r >> 1) & 1) of their two 256-byte lines.  A tap moves the address by
+// 4096 bytes, a step by 2048 and the second read by 512, all whole lines that
+// leave r & 3 alone: one base address per tile, everything else an immediate
+// offset.  The copy's 16-byte writes go out 16 lanes a pass, which are the 16
+// vectors of rows 2v, 2v+1: one whole line, conflict-free under any
+// permutation of its cells.  Every address is a multiple of 8 and inside the
+// buffer, and the reads are in no divergent branch: EXEC is all ones.
+//
+// Staging, barriers and the order of every accumulator's chain over (chunk,
+// tap, step) are the forward's: the same bits every run.
+template <bool RES>
+__global__ __launch_bounds__(kT) void conv3x3_bwd_data(
+    const uint4* __restrict__ dy, const uint4* __restrict__ w,
+    uint4* __restrict__ dx, Conv3x3FwdPlan p) {
+  extern __shared__ uint4 lds[];
+  constexpr int BN = kConv3x3FwdBn, M = kConv3x3FwdTileRows;
+  constexpr int kTapBytes = kConv3x3FwdKc * BN * 2;  // [32 n][64 c]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int c = lane & 31, h = lane >> 5;
+  const int c0 = conv3x3_fwd_ntile(p, blockIdx.x) * BN;  // of dX's channels
+  const int split = conv3x3_fwd_split(p, blockIdx.x);
+  const int nvec = p.n / 8;
+  const int xbuf = p.xvecs * kT;      // vectors of a strip buffer
+  uint4* wimg = lds;                  // two weight chunks
+  uint4* ximg = lds + 2 * kFwdWVecs;  // two strips
+  uint4* stage = ximg + 2 * xbuf + wave * 256;  // [32 rows][64 channels]
+
+  if (RES) {  // the two chunks are the two buffers, for good
+    for (int idx = tid; idx < 2 * kFwdWVecs; idx += kT) {
+      const int kc = idx / kFwdWVecs, v = idx % kFwdWVecs;
+      wimg[kc * kFwdWVecs + bwd_w_slot(v)] = *bwd_w_src(w, p, c0, kc, v);
+    }
+  }
+
+  FwdStage<RES, true> st;
+  int tile = split, kc = 0, buf = 0;  // split < row_tiles
+  st.load(dy, w, p, c0, tile, 0, tid);
+  st.store(wimg, ximg, p, tid);
+
+  // as conv1x1_wrw: lane 4q+pp of a 16-lane group supplies row 8h+q of the
+  // step's first read, channels 4pp .. 4pp+3 of its half of tile j's cell
+  int bb[2];
+#pragma unroll
+  for (int j = 0; j < 2; j++)
+    bb[j] = wrw_cell<BN>(8 * h + ((lane >> 2) & 3), j) +
+            32 * ((lane >> 4) & 1) + 8 * (lane & 3);
+
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int s = 0; s < 2; s++)
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+      for (int e = 0; e < 16; e++) acc[s][j][e] = 0.f;
+  unsigned valid[2] = {0, 0};
+
+  while (tile < p.row_tiles) {
+    // as conv3x3_stats: the next stage is loaded before the MFMAs of this one
+    int nkc = kc + 1, ntl = tile;
+    if (nkc == p.nchunks) nkc = 0, ntl = tile + p.splits;
+    const bool more = ntl < p.row_tiles;
+    if (more) st.load(dy, w, p, c0, ntl, nkc, tid);
+    // buffer `buf` is written, and the other one, read a stage ago, is free
+    __syncthreads();
+    if (kc == 0) {
+#pragma unroll
+      for (int s = 0; s < 2; s++)
+        valid[s] = conv3x3_fwd_taps(p, tile * M + wave * 64 + s * 32 + c);
+    }
+    char* wl = reinterpret_cast<char*>(wimg + buf * kFwdWVecs);
+    const uint4* xl = ximg + buf * xbuf;
+    uint4 av[2][2];  // the operands of this step and the next
+    bf16x8 bv[2][2];
+    auto read = [&](int u) {
+      const int tap = u >> 1, q = 2 * (u & 1) + h;
+#pragma unroll
+      for (int s = 0; s < 2; s++) {
+        const int j = conv3x3_fwd_strip_index(p, wave * 64 + s * 32 + c, tap);
+        const uint4 v = xl[fwd_slot(j, q)];
+        const unsigned m = 0u - ((valid[s] >> tap) & 1u);
+        av[u & 1][s] = make_uint4(v.x & m, v.y & m, v.z & m, v.w & m);
+      }
+#pragma unroll
+      for (int j = 0; j < 2; j++)  // the mirrored tap
+        bv[u & 1][j] = wrw_operand<BN>(wl + (8 - tap) * kTapBytes, bb[j], u & 1);
+    };
+    read(0);
+#pragma unroll
+    for (int u = 0; u < 18; u++) {
+      if (u + 1 < 18) read(u + 1);
+#pragma unroll
+      for (int s = 0; s < 2; s++)
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+          acc[s][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              __builtin_bit_cast(bf16x8, av[u & 1][s]), bv[u & 1][j],
+              acc[s][j], 0, 0, 0);
+    }
+    // nothing that waits for the loads above may move up among the MFMAs
+    __builtin_amdgcn_sched_barrier(0);
+    buf ^= 1;
+    if (more) st.store(wimg + buf * kFwdWVecs, ximg + buf * xbuf, p, tid);
+
+    if (nkc == 0) {  // the tile is complete: round once and store
+#pragma unroll
+      for (int s = 0; s < 2; s++) {
+        const int r0 = tile * M + wave * 64 + s * 32;
+        const int live = p.rows - r0 < 32 ? p.rows - r0 : 32;  // may be <= 0
+        unsigned pk[2][8];
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+          for (int e = 0; e < 8; e++)
+            pk[j][e] = fwd_pack_bf16(acc[s][j][2 * e], acc[s][j][2 * e + 1]);
+        fwd_store_subtile(pk, stage, dx, r0, live, nvec, c0, lane);
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+          for (int e = 0; e < 16; e++) acc[s][j][e] = 0.f;
+      }
+    }
+    kc = nkc, tile = ntl;
+  }
+}
+
+template <bool RES>
+void launch_bwd3x3(const Conv3x3FwdPlan& p, const void* dy, const void* w,
+                   void* dx, hipStream_t stream) {
+  static const hipError_t attr = hipFuncSetAttribute(
+      reinterpret_cast<const void*>(&conv3x3_bwd_data<RES>),
+      hipFuncAttributeMaxDynamicSharedMemorySize, kConvLdsBytes);
+  CGX_HIP_CHECK(attr);
+  hipLaunchKernelGGL((conv3x3_bwd_data<RES>), dim3(p.grid), dim3(kT),
+                     p.lds_bytes, stream, static_cast<const uint4*>(dy),
+                     static_cast<const uint4*>(w), static_cast<uint4*>(dx), p);
+  CGX_HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace
+
+void launch_conv3x3_bwd_data(const Conv3x3FwdPlan& p, const void* dy,
+                             const void* w, void* dx, hipStream_t stream) {
+  TORCH_CHECK(p.eligible, "conv3x3_bwd_data: shape is not eligible");
+  TORCH_CHECK(p.bn == kConv3x3FwdBn && p.kc == kConv3x3FwdKc &&
+                  p.xvecs <= kConv3x3FwdXVecs &&
+                  p.strip_rows <= 64 * p.xvecs && p.splits <= p.row_tiles &&
+                  p.resident == (p.nchunks == 2) &&
+                  p.lds_bytes <= kConvLdsBytes,
+              "conv3x3_bwd_data: plan and kernel disagree");
+  if (p.resident) launch_bwd3x3<true>(p, dy, w, dx, stream);
+  else launch_bwd3x3<false>(p, dy, w, dx, stream);
+}
 
 void launch_conv3x3_stats(const Conv3x3FwdPlan& p, const void* x, const void* w,
                           void* y, float* part, hipStream_t stream) {

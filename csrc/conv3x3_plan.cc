@@ -1,4 +1,5 @@
-// Launch geometry of the 3x3 weight gradient and forward: see conv3x3_plan.h.
+// Launch geometry of the 3x3 weight gradient, forward and input gradient: see
+// conv3x3_plan.h.
 #include "conv3x3_plan.h"
 
 #include <algorithm>
@@ -26,6 +27,16 @@ constexpr Measured3x3 kNativeWrw3x3[] = {
 // (benchmarks/conv3x3_fwd_shapes.py).  All four bottleneck problems of
 // ResNet-50 at batch 256 met it.
 constexpr Measured3x3 kNativeFwd3x3[] = {
+    {256, 56, 56, 64, 64},
+    {256, 28, 28, 128, 128},
+    {256, 14, 14, 256, 256},
+    {256, 7, 7, 512, 512},
+};
+
+// The same rule for conv3x3_bwd_data against MIOpen's backward-data alone
+// (benchmarks/conv3x3_bwd_shapes.py); here batch, H, W, C of dX, N of dY.
+// All four met it as well.
+constexpr Measured3x3 kNativeBwd3x3[] = {
     {256, 56, 56, 64, 64},
     {256, 28, 28, 128, 128},
     {256, 14, 14, 256, 256},
@@ -171,6 +182,18 @@ Conv3x3FwdPlan conv3x3_fwd_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
                 kConvStageBytes;
   p.pstride = 2 * p.n + p.ntiles;
   p.partial_floats = (int64_t)p.splits * p.pstride;
+  return p;
+}
+
+Conv3x3FwdPlan conv3x3_bwd_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
+                                int64_t n, int64_t max_workgroups) {
+  Conv3x3FwdPlan p = conv3x3_fwd_plan(batch, h, w, n, c, max_workgroups);
+  p.native = false;
+  p.pstride = 0;
+  p.partial_floats = 0;
+  if (!p.eligible) return p;
+  for (const Measured3x3& m : kNativeBwd3x3)
+    p.native |= m.batch == batch && m.h == h && m.w == w && m.c == c && m.n == n;
   return p;
 }
 

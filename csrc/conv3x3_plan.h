@@ -1,6 +1,7 @@
 // Launch geometry of the weight gradient of a 3x3 / stride 1 / padding 1
 // convolution (conv3x3_wrw in conv3x3_kernels.hip) and, further down, of its
-// forward with BatchNorm partials (conv3x3_stats).
+// forward with BatchNorm partials (conv3x3_stats) and of its input gradient
+// (conv3x3_bwd_data).
 //
 // Pure host arithmetic, like conv1x1_plan.h.  dW[n, c, r, s] = sum over b, h, w
 // of dY[b, n, h, w] * X[b, c, h+r-1, w+s-1] on channels_last bf16 tensors is
@@ -194,5 +195,23 @@ __host__ __device__ inline unsigned conv3x3_fwd_taps(const Conv3x3FwdPlan& p,
 // w[N, 3, 3, C] bf16; every pointer 16-byte aligned.
 void launch_conv3x3_stats(const Conv3x3FwdPlan& p, const void* x, const void* w,
                           void* y, float* part, hipStream_t stream);
+
+// ---- input gradient (conv3x3_bwd_data) ----------------------------------------
+//
+// dX[R, C] = sum over the nine taps t of dY_t[R, N] * W_{8-t}[N, C]: the
+// forward's GEMM with the roles of C and N exchanged, on the same strip with
+// the same validity bits (H, W and the padding are the forward's).  So the
+// plan is the forward's plan of the exchanged problem, and its fields keep
+// the kernel's meaning: `c` is the contraction depth, the N of dY, and `n` the
+// output width, the C of dX; `nchunks` and `resident` follow N, `ntiles` C.
+// There are no partials: pstride and partial_floats are 0.  `native` comes
+// from a table of its own.  Eligibility is the forward's.
+Conv3x3FwdPlan conv3x3_bwd_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
+                                int64_t n, int64_t max_workgroups = 0);
+
+// dx[B, H, W, C] bf16 from dy[B, H, W, N] and w[N, 3, 3, C] bf16, the
+// convolution's own weight, read transposed; every pointer 16-byte aligned.
+void launch_conv3x3_bwd_data(const Conv3x3FwdPlan& p, const void* dy,
+                             const void* w, void* dx, hipStream_t stream);
 
 }  // namespace cgx

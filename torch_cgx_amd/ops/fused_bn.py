@@ -60,7 +60,10 @@ of the 1x1 one; ``CGX_NATIVE_CONV3X3_WRW`` switches it like the others and
 depends on none of them.  ``conv3x3_bn_act(conv, bn, x)`` is
 ``bn_act(bn, conv3x3(conv, x))`` with a native forward as well
 (``_C.conv3x3_stats``), which hands ``bn`` its statistics as the 1x1 forward
-does; ``CGX_NATIVE_CONV3X3`` switches it, on its own.
+does; ``CGX_NATIVE_CONV3X3`` switches it, on its own.  The input gradient of
+both has the forward's implicit GEMM with the taps mirrored and the weight
+read transposed (``_C.conv3x3_bwd_data``); ``CGX_NATIVE_CONV3X3_BWD`` switches
+it, on its own as well.
 
 ``CGX_FUSED_BN=0`` switches all native paths off.
 """
@@ -430,15 +433,16 @@ class _Conv3x3(torch.autograd.Function):
     native implicit GEMM with the BatchNorm partials of ``y``
     (``_C.conv3x3_stats``) where ``native_fwd`` says so, else stock with
     ``part`` None.  With ``native_wrw`` the weight gradient comes from the
-    native implicit GEMM (``_C.conv3x3_wrw``) where it takes the gradient that
-    arrives, else from the stock backward; the input gradient is the stock
-    one."""
+    native implicit GEMM (``_C.conv3x3_wrw``) and with ``native_bwd`` the
+    input gradient from ``_C.conv3x3_bwd_data``, each where it takes the
+    gradient that arrives; the stock backward computes what remains."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
-    def forward(ctx, x, weight, native_fwd, native_wrw):
+    def forward(ctx, x, weight, native_fwd, native_wrw, native_bwd=False):
         ctx.save_for_backward(x, weight)
         ctx.native_wrw = native_wrw
+        ctx.native_bwd = native_bwd
         if native_fwd:
             y, part = _C.conv3x3_stats(x, weight)
             ctx.mark_non_differentiable(part)
@@ -453,12 +457,16 @@ class _Conv3x3(torch.autograd.Function):
         dx = dw = None
         if need_dw and ctx.native_wrw and _C.conv3x3_wrw_eligible(dy, x):
             dw, need_dw = _C.conv3x3_wrw(dy, x), False
+        if (need_dx and ctx.native_bwd
+                and _C.conv3x3_bwd_eligible(dy, weight)):
+            dx, need_dx = _C.conv3x3_bwd_data(dy, weight), False
         if need_dx or need_dw:
-            dx, dw_stock, _ = torch.ops.aten.convolution_backward(
+            dx_stock, dw_stock, _ = torch.ops.aten.convolution_backward(
                 dy, x, weight, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1,
                 (need_dx, need_dw, False))
+            dx = dx_stock if need_dx else dx
             dw = dw_stock if need_dw else dw
-        return dx, dw, None, None
+        return dx, dw, None, None, None
 
 
 def native_conv3x3_wrw_mode() -> str:
@@ -479,16 +487,25 @@ def native_conv3x3_mode() -> str:
     return os.environ.get("CGX_NATIVE_CONV3X3", "1")
 
 
+def native_conv3x3_bwd_mode() -> str:
+    """``CGX_NATIVE_CONV3X3_BWD``, the switch of the input gradient, with the
+    values of ``CGX_NATIVE_CONV3X3_WRW`` and as independent."""
+    if not fused_bn_enabled():
+        return "0"
+    return os.environ.get("CGX_NATIVE_CONV3X3_BWD", "1")
+
+
 def _conv3x3(conv, x, bn=None):
     """``(conv(x), part)``.  For a bias-free 3x3 / stride 1 / padding 1
     convolution of a channels_last bf16 CUDA activation it goes through
     ``_Conv3x3`` where the native forward (only with a training ``bn`` to
-    take its partials) or the native weight gradient is to run, each by its
-    own switch and its plan's table; in every other case it is the module
-    call itself and ``part`` is None."""
+    take its partials), the native weight gradient or the native input
+    gradient is to run, each by its own switch and its plan's table; in every
+    other case it is the module call itself and ``part`` is None."""
     fwd_mode = native_conv3x3_mode() if bn is not None else "0"
     wrw_mode = native_conv3x3_wrw_mode() if torch.is_grad_enabled() else "0"
-    if fwd_mode == "0" and wrw_mode == "0":
+    bwd_mode = native_conv3x3_bwd_mode() if torch.is_grad_enabled() else "0"
+    if fwd_mode == "0" and wrw_mode == "0" and bwd_mode == "0":
         return conv(x), None
     if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == (3, 3)
             and conv.stride == (1, 1) and conv.padding == (1, 1)
@@ -518,14 +535,16 @@ def _conv3x3(conv, x, bn=None):
            and w.is_contiguous(memory_format=torch.channels_last)
            and (w.dtype != torch.bfloat16 or _C.conv3x3_fwd_eligible(x, w)))
     wrw = w.requires_grad and takes(wrw_mode, _C.conv3x3_wrw_plan(*shape))
-    if not (fwd or wrw):
+    bwd = x.requires_grad and takes(bwd_mode, _C.conv3x3_bwd_plan(*shape))
+    if not (fwd or wrw or bwd):
         return conv(x), None
-    return _Conv3x3.apply(x, w, fwd, wrw)
+    return _Conv3x3.apply(x, w, fwd, wrw, bwd)
 
 
 def conv3x3(conv: torch.nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
     """``conv(x)``, through ``_Conv3x3`` where the native weight gradient is
-    to compute the gradient of its weight (``native_conv3x3_wrw_mode``)."""
+    to compute the gradient of its weight (``native_conv3x3_wrw_mode``) or
+    the native input gradient that of ``x`` (``native_conv3x3_bwd_mode``)."""
     return _conv3x3(conv, x)[0]
 
 
