@@ -23,6 +23,7 @@
 #include "collectives.h"
 #include "conv1x1_plan.h"
 #include "conv3x3_plan.h"
+#include "conv_stem_plan.h"
 #include "reducer.h"
 
 namespace cgx {
@@ -839,7 +840,8 @@ BnPoolPlan bn_pool_plan_of(const at::Tensor& x) {
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
 py_bn_act_pool_forward(const at::Tensor& x, const at::Tensor& weight,
                        const at::Tensor& bias, at::Tensor running_mean,
-                       at::Tensor running_var, double momentum, double eps) {
+                       at::Tensor running_var, double momentum, double eps,
+                       const c10::optional<at::Tensor>& stats_part) {
   TORCH_CHECK(py_bn_eligible(x), "bn_act_pool_forward: input is not eligible");
   const BnPlan p = bn_plan_of(x);
   const BnPoolPlan g = bn_pool_plan_of(x);
@@ -866,6 +868,11 @@ py_bn_act_pool_forward(const at::Tensor& x, const at::Tensor& weight,
   a.out = out.data_ptr();
   a.arg = arg.data_ptr<uint8_t>();
   a.part = part.data_ptr<float>();
+  BnPartials ext;
+  if (stats_part.has_value()) {
+    ext = bn_external_partials(*stats_part, x);
+    a.stats = &ext;
+  }
   launch_bn_pool_forward(p, g, a, bn_stream(x));
   return {out, mean, invstd, arg};
 }
@@ -1432,6 +1439,136 @@ py::dict py_conv3x3_fwd_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
                              int64_t n, int64_t max_workgroups) {
   return conv3x3_fwd_plan_dict(
       conv3x3_fwd_plan(batch, h, w, c, n, max_workgroups));
+}
+
+// ---- stem convolution forward with statistics ---------------------------------
+
+// x as the BatchNorm kernels take it, with three channels, and a dense,
+// 16-byte aligned bf16 [64, 3, 7, 7] weight in channels_last, whose memory is
+// [64][7][7][3].
+bool py_conv_stem_eligible(const at::Tensor& x, const at::Tensor& w) {
+  return bn_tensor_ok(x) && x.size(1) == kConvStemC && w.is_cuda() &&
+         w.device() == x.device() && w.scalar_type() == at::kBFloat16 &&
+         w.dim() == 4 && w.size(0) == kConvStemN && w.size(1) == kConvStemC &&
+         w.size(2) == kConvStemTaps && w.size(3) == kConvStemTaps &&
+         w.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+         reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0 &&
+         conv_stem_plan(x.size(0), x.size(2), x.size(3)).eligible;
+}
+
+// conv2d(x, weight, stride=2, padding=3) -> (y, part); part holds the
+// BatchNorm partials of y in the layout of conv1x1_stats
+std::tuple<at::Tensor, at::Tensor> py_conv_stem_stats(const at::Tensor& x,
+                                                      const at::Tensor& weight,
+                                                      int64_t max_workgroups) {
+  TORCH_CHECK(max_workgroups >= 0, "conv_stem_stats: max_workgroups >= 0");
+  TORCH_CHECK(py_conv_stem_eligible(x, weight),
+              "conv_stem_stats: input or weight is not eligible");
+  const ConvStemPlan p =
+      conv_stem_plan(x.size(0), x.size(2), x.size(3), max_workgroups);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device().index());
+  auto y = at::empty({x.size(0), kConvStemN, p.oh, p.ow}, x.options(),
+                     at::MemoryFormat::ChannelsLast);
+  auto part = at::empty({p.splits, p.pstride}, x.options().dtype(at::kFloat));
+  launch_conv_stem_stats(p, x.data_ptr(), weight.data_ptr(), y.data_ptr(),
+                         part.data_ptr<float>(), bn_stream(x));
+  return {y, part};
+}
+
+py::dict py_conv_stem_plan(int64_t batch, int64_t h, int64_t w,
+                           int64_t max_workgroups) {
+  const ConvStemPlan p = conv_stem_plan(batch, h, w, max_workgroups);
+  py::dict d;
+  d["eligible"] = p.eligible;
+  d["native"] = p.native;
+  d["threads"] = kConvThreads;
+  d["oh"] = p.oh;
+  d["ow"] = p.ow;
+  d["rows"] = p.rows;
+  d["band_rows"] = p.band_rows;
+  d["bands"] = p.bands;
+  d["tiles_per_band"] = p.tiles_per_band;
+  d["tile"] = kConvStemTile;
+  d["in_rows"] = p.in_rows;
+  d["pitch"] = p.pitch;
+  d["xvecs"] = p.xvecs;
+  d["max_w"] = kConvStemMaxW;
+  d["splits"] = p.splits;
+  d["grid"] = p.grid;
+  d["bands_per_split"] = p.bands_per_split;
+  d["run"] = p.run;
+  d["lds_bytes"] = p.lds_bytes;
+  d["lds_budget"] = kConvLdsBytes;
+  d["pstride"] = p.pstride;
+  d["partial_floats"] = p.partial_floats;
+  return d;
+}
+
+// Test seam: the kernel's walk replayed on the host.  Entry [wg, i] holds
+// (row0, row1, tiles) of the i-th band of workgroup wg: the output pixels it
+// covers and the 32-pixel tiles its waves share; -1 once it has run out of
+// bands.
+at::Tensor py_conv_stem_walk(int64_t batch, int64_t h, int64_t w,
+                             int64_t max_workgroups) {
+  const ConvStemPlan p = conv_stem_plan(batch, h, w, max_workgroups);
+  TORCH_CHECK(p.eligible, "conv_stem_walk: shape is not eligible");
+  auto out = at::full({p.grid, p.bands_per_split, 3}, -1,
+                      at::TensorOptions().dtype(at::kLong));
+  int64_t* o = out.data_ptr<int64_t>();
+  for (int wg = 0; wg < p.grid; wg++) {
+    int i = 0;
+    for (int band = wg; band < p.bands; band += p.splits, i++) {
+      TORCH_CHECK(i < p.bands_per_split, "conv_stem_walk: walk too long");
+      const ConvStemBand b = conv_stem_band(p, band);
+      int64_t* e = o + ((int64_t)wg * p.bands_per_split + i) * 3;
+      e[0] = ((int64_t)b.image * p.oh + b.oh0) * p.ow;
+      e[1] = e[0] + (int64_t)b.live * p.ow;
+      e[2] = (b.live * p.ow + kConvStemTile - 1) / kConvStemTile;
+      TORCH_CHECK(e[2] <= p.tiles_per_band, "conv_stem_walk: too many tiles");
+    }
+  }
+  return out;
+}
+
+// Test seam: entry [row - row0, k] is the element of x (pixel * 3 + channel)
+// that the kernel multiplies with position k of the padded filter, 24r + 3s +
+// c, for output pixel `row`, read through the strip of the row's band; -1
+// where the strip holds a zero there or the operand is cleared.
+at::Tensor py_conv_stem_taps(int64_t batch, int64_t h, int64_t w, int64_t row0,
+                             int64_t row1) {
+  const ConvStemPlan p = conv_stem_plan(batch, h, w);
+  TORCH_CHECK(p.eligible, "conv_stem_taps: shape is not eligible");
+  TORCH_CHECK(0 <= row0 && row0 <= row1 && row1 <= p.rows,
+              "conv_stem_taps: rows out of range");
+  constexpr int K = 8 * kConvStemGroups;
+  auto out = at::empty({row1 - row0, K}, at::TensorOptions().dtype(at::kLong));
+  int64_t* o = out.data_ptr<int64_t>();
+  for (int64_t row = row0; row < row1; row++) {
+    const int image = (int)(row / (p.oh * p.ow));
+    const int oh = (int)(row / p.ow) % p.oh;
+    const int band = image * p.bands_per_image + oh / p.band_rows;
+    const ConvStemBand b = conv_stem_band(p, band);
+    const int pl = (int)(row - ((int64_t)image * p.oh + b.oh0) * p.ow);
+    TORCH_CHECK(pl >= 0 && pl < b.live * p.ow, "conv_stem_taps: off the band");
+    const int at0 = conv_stem_operand(p, pl);
+    for (int group = 0; group < kConvStemGroups; group++) {
+      // the pad group reads the one before it, as the kernel does
+      const int at = at0 + conv_stem_group_offset(
+                               p, std::min(group, kConvStemGroups - 2));
+      TORCH_CHECK(at % 4 == 0 && at + 16 <= p.in_rows * p.pitch,
+                  "conv_stem_taps: off the strip");
+      for (int i = 0; i < 8; i++) {
+        const unsigned keep = conv_stem_keep(group, i / 2) >> (16 * (i & 1));
+        const int byte = at + 2 * i;
+        const ConvStemSrc s = conv_stem_src(p, b, byte / 16);
+        const int sub = byte % 16 / 2;
+        const int elem = sub == 0 ? s.elem : s.vec >= 0 ? 8 * s.vec + sub - 1 : -1;
+        o[(row - row0) * K + 8 * group + i] =
+            (keep & 0xffffu) && elem >= 0 ? (int64_t)s.row * 3 * p.w + elem : -1;
+      }
+    }
+  }
+  return out;
 }
 
 // ---- 3x3 convolution input gradient -------------------------------------------
@@ -2018,6 +2155,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("h"), py::arg("w"), py::arg("c"), py::arg("n"),
         "Test seam: [rows, 9] int64, the pixel each tap of each output pixel "
         "reads through its tile's strip, -1 where the operand is cleared.");
+  m.def("conv_stem_stats", &cgx::py_conv_stem_stats, py::arg("x"),
+        py::arg("weight"), py::arg("max_workgroups") = 0,
+        "conv2d(x, weight, stride=2, padding=3) of the 3 -> 64 channel 7x7 "
+        "stem by the native implicit GEMM -> (y, part): part are the "
+        "BatchNorm partials of y, in the layout of conv1x1_stats, for "
+        "bn_act_pool_forward.  max_workgroups > 0 caps the grid.");
+  m.def("conv_stem_eligible", &cgx::py_conv_stem_eligible, py::arg("x"),
+        py::arg("weight"),
+        "True where conv_stem_stats takes (x, weight): CUDA, bf16, dense "
+        "channels_last and 16-byte aligned, [B, 3, H, W] with H even and W a "
+        "multiple of 8 up to 768, and a [64, 3, 7, 7] weight.");
+  m.def("conv_stem_plan", &cgx::py_conv_stem_plan, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("max_workgroups") = 0,
+        "The launch geometry of conv_stem_stats, and `native`: whether the "
+        "model uses it for this problem.");
+  m.def("conv_stem_walk", &cgx::py_conv_stem_walk, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("max_workgroups") = 0,
+        "Test seam: [grid, bands_per_split, 3] int64, (row0, row1, tiles) of "
+        "every band a workgroup of conv_stem_stats walks (-1: none).");
+  m.def("conv_stem_taps", &cgx::py_conv_stem_taps, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("row0"), py::arg("row1"),
+        "Test seam: [row1 - row0, 176] int64, the element of x each position "
+        "of the padded filter meets for the output pixels row0 .. row1-1, "
+        "read through the band's strip; -1 where it is zero or cleared.");
   m.def("bn_act2_backward", &cgx::py_bn_act2_backward,
         "Backward of bn_act2_forward: (dy, x3, xd, mean3, invstd3, weight3, "
         "meand, invstdd, weightd, mask) -> (dx3, dxd, dgamma3, dbeta3, "
@@ -2025,8 +2186,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_act_pool_forward", &cgx::py_bn_act_pool_forward, py::arg("x"),
         py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
         py::arg("running_var"), py::arg("momentum"), py::arg("eps"),
+        py::arg("part") = py::none(),
         "max_pool2d(relu(bn(x)), 3, 2, 1) in training mode -> (pooled, mean, "
-        "invstd, arg); arg is one byte per pooled element.");
+        "invstd, arg); arg is one byte per pooled element.  With `part`, the "
+        "partials conv_stem_stats left for x, the statistics pass is "
+        "skipped.");
   m.def("bn_act_pool_backward", &cgx::py_bn_act_pool_backward, py::arg("dy"),
         py::arg("x"), py::arg("mean"), py::arg("invstd"), py::arg("weight"),
         py::arg("arg"),

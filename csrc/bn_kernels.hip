@@ -914,7 +914,7 @@ void launch_bn_join_backward(const BnPlan& p, const BnJoinArgs& j,
 
 void launch_bn_pool_forward(const BnPlan& p, const BnPoolPlan& g,
                             const BnPoolArgs& a, hipStream_t stream) {
-  launch_bn_stats(p, a.x, a.part, nullptr, a.mean, a.invstd, a.running_mean,
+  launch_bn_stats(p, a.x, a.part, a.stats, a.mean, a.invstd, a.running_mean,
                   a.running_var, a.momentum, a.eps, stream);
   hipLaunchKernelGGL(bn_apply_pool, dim3(g.grid), dim3(kT), 0, stream,
                      static_cast<const uint4*>(a.x), a.mean, a.invstd, a.weight,

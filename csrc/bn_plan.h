@@ -205,6 +205,7 @@ struct BnPoolArgs {
   float* dgamma;
   float* dbeta;
   float* part;      // as for launch_bn_forward
+  const BnPartials* stats = nullptr;  // forward only, as in BnForwardArgs
 };
 void launch_bn_pool_forward(const BnPlan& p, const BnPoolPlan& g,
                             const BnPoolArgs& a, hipStream_t stream);

@@ -19,6 +19,7 @@ SOURCES = [
     "csrc/bn_kernels.hip",
     "csrc/conv1x1_kernels.hip",
     "csrc/conv3x3_kernels.hip",
+    "csrc/conv_stem_kernels.hip",
     "csrc/compress.cc",
     "csrc/config.cc",
     "csrc/registry.cc",
@@ -26,6 +27,7 @@ SOURCES = [
     "csrc/bn_plan.cc",
     "csrc/conv1x1_plan.cc",
     "csrc/conv3x3_plan.cc",
+    "csrc/conv_stem_plan.cc",
     "csrc/phase_timer.cc",
     "csrc/engine.cc",
     "csrc/transport.cc",
@@ -39,7 +41,8 @@ HEADERS = ["csrc/compress.h", "csrc/check.h", "csrc/config.h",
            "csrc/engine.h", "csrc/backend.h", "csrc/transport.h",
            "csrc/reducer.h", "csrc/bn_plan.h", "csrc/collectives.h",
            "csrc/bn_moments.h", "csrc/conv1x1_plan.h",
-           "csrc/conv3x3_plan.h", "csrc/wrw_image.h"]
+           "csrc/conv3x3_plan.h", "csrc/wrw_image.h",
+           "csrc/conv_stem_plan.h", "csrc/conv_epilogue.h"]
 EXT_OUT = os.path.join(
     "torch_cgx_amd", "_C" + sysconfig.get_config_var("EXT_SUFFIX"))
 
@@ -81,10 +84,11 @@ def build(verbose: bool = True) -> str:
             # contraction would fold this into one rounding and break
             # byte-parity with the golden wire-format model
             extra = ["-ffp-contract=off"]
-        if src == "csrc/conv3x3_kernels.hip":
+        if src in ("csrc/conv3x3_kernels.hip",
+                   "csrc/conv_stem_kernels.hip"):
             # keeps the compiler from forming v_pk_{add,mul,fma}_f32 in new
-            # kernels.  A guard only: this kernel has none with or without
-            # the flag, which merely shifts its register allocation
+            # kernels.  A guard only: these kernels have none with or without
+            # the flag, which merely shifts their register allocation
             # (benchmarks/RESULTS.md)
             extra += ["-Xclang", "-target-feature", "-Xclang",
                       "-packed-fp32-ops"]

@@ -11,8 +11,8 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from ..ops.fused_bn import (bn_act, bn_act_pool, conv3x3_bn_act, conv_bn_act,
-                            conv_bn_act_fork)
+from ..ops.fused_bn import (bn_act, conv3x3_bn_act, conv_bn_act,
+                            conv_bn_act_fork, conv_stem_bn_act_pool)
 
 
 class Bottleneck(nn.Module):
@@ -86,7 +86,7 @@ class ResNet(nn.Module):
         return nn.Sequential(*layers)
 
     def forward(self, x):
-        x = bn_act_pool(self.bn1, self.conv1(x), self.maxpool)
+        x = conv_stem_bn_act_pool(self.conv1, self.bn1, x, self.maxpool)
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         x = self.avgpool(x).flatten(1)
         return self.fc(x)

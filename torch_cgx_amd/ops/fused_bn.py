@@ -65,6 +65,16 @@ both has the forward's implicit GEMM with the taps mirrored and the weight
 read transposed (``_C.conv3x3_bwd_data``); ``CGX_NATIVE_CONV3X3_BWD`` switches
 it, on its own as well.
 
+``conv_stem_bn_act_pool(conv, bn, x, pool)`` is
+``bn_act_pool(bn, conv(x), pool)`` for the stem, ``Conv2d(3, 64, 7, stride=2,
+padding=3)``.  Its forward has a native implicit GEMM built for three input
+channels (``_C.conv_stem_stats``, csrc/conv_stem_kernels.hip), which hands
+``bn`` its statistics as the other forwards do, so that the stem's statistics
+pass disappears; its weight gradient is the stock one and it has no input
+gradient to speak of.  ``CGX_NATIVE_CONV_STEM`` switches it like the others
+(``0`` off, ``all`` every eligible problem, by default those its plan's table
+has measured faster) and depends on none of them.
+
 ``CGX_FUSED_BN=0`` switches all native paths off.
 """
 
@@ -124,9 +134,9 @@ class _BnActJoin(torch.autograd.Function):
 class _BnActPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum,
-                eps):
+                eps, part=None):
         out, mean, invstd, arg = _C.bn_act_pool_forward(
-            x, weight, bias, running_mean, running_var, momentum, eps)
+            x, weight, bias, running_mean, running_var, momentum, eps, part)
         ctx.save_for_backward(x, mean, invstd, weight, arg)
         return out
 
@@ -135,18 +145,23 @@ class _BnActPool(torch.autograd.Function):
         x, mean, invstd, weight, arg = ctx.saved_tensors
         dx, dgamma, dbeta = _C.bn_act_pool_backward(dy, x, mean, invstd,
                                                     weight, arg)
-        return (dx, dgamma, dbeta, None, None, None, None)
+        return (dx, dgamma, dbeta, None, None, None, None, None)
 
 
 def fused_bn_enabled() -> bool:
     return os.environ.get("CGX_FUSED_BN", "1") != "0"
 
 
+def _bn_native(bn) -> bool:
+    """What the native kernels ask of the module, whatever its input."""
+    return (bn.training and bn.track_running_stats
+            and bn.momentum is not None and fused_bn_enabled()
+            and bn.weight is not None and bn.bias is not None
+            and bn.weight.dtype == torch.float32)
+
+
 def _native(bn, x, identity) -> bool:
-    if not (bn.training and bn.track_running_stats
-            and bn.momentum is not None and fused_bn_enabled()):
-        return False
-    if bn.weight is None or bn.bias is None:
+    if not _bn_native(bn):
         return False
     if not (x.is_cuda and _C.bn_eligible(x)):
         return False
@@ -154,7 +169,7 @@ def _native(bn, x, identity) -> bool:
             identity.shape == x.shape and identity.device == x.device
             and _C.bn_eligible(identity)):
         return False
-    return bn.weight.dtype == torch.float32
+    return True
 
 
 def _bn_args(bn):
@@ -568,9 +583,95 @@ def _pool_is_3x3_s2_p1(pool) -> bool:
 
 
 def bn_act_pool(bn: torch.nn.BatchNorm2d, x: torch.Tensor,
-                pool: torch.nn.Module) -> torch.Tensor:
-    """``pool(relu(bn(x)))``."""
+                pool: torch.nn.Module, part: torch.Tensor = None
+                ) -> torch.Tensor:
+    """``pool(relu(bn(x)))``.  ``part`` are the statistics partials that came
+    with ``x`` from the native stem convolution, if it produced them."""
     if _pool_is_3x3_s2_p1(pool) and _native(bn, x, None):
         bn.num_batches_tracked.add_(1)
-        return _BnActPool.apply(x, *_bn_args(bn))
-    return pool(bn_act(bn, x))
+        return _BnActPool.apply(x, *_bn_args(bn), part)
+    return pool(bn_act(bn, x, part=part))
+
+
+class _ConvStem(torch.autograd.Function):
+    """``(y, part) = f(x, weight)``: ``conv2d(x, weight, stride=2,
+    padding=3)``, by the native implicit GEMM with the BatchNorm partials of
+    ``y`` (``_C.conv_stem_stats``) where ``native_fwd`` says so, else stock
+    with ``part`` None.  The backward is the stock one."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
+    def forward(ctx, x, weight, native_fwd):
+        ctx.save_for_backward(x, weight)
+        if native_fwd:
+            y, part = _C.conv_stem_stats(x, weight)
+            ctx.mark_non_differentiable(part)
+            return y, part
+        return F.conv2d(x, weight, None, 2, 3), None
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dy, _dpart):
+        x, weight = ctx.saved_tensors
+        need_dx, need_dw = ctx.needs_input_grad[:2]
+        dx, dw, _ = torch.ops.aten.convolution_backward(
+            dy, x, weight, None, (2, 2), (3, 3), (1, 1), False, (0, 0), 1,
+            (need_dx, need_dw, False))
+        return (dx if need_dx else None), (dw if need_dw else None), None
+
+
+def native_conv_stem_mode() -> str:
+    """``CGX_NATIVE_CONV_STEM``, the switch of the stem's forward with
+    statistics: "0" off, "all" every eligible problem, else ("1", the
+    default) the problems its plan has measured faster.  Off where
+    ``CGX_FUSED_BN`` is; no other switch reaches it."""
+    if not fused_bn_enabled():
+        return "0"
+    return os.environ.get("CGX_NATIVE_CONV_STEM", "1")
+
+
+def _conv_stem_native(conv, bn, x, pool) -> bool:
+    """Whether ``_C.conv_stem_stats`` is to compute ``conv(x)`` for ``bn``
+    and ``pool``: the switch and the plan say so and the modules and tensors
+    are what the kernels take."""
+    mode = native_conv_stem_mode()
+    if mode == "0":
+        return False
+    if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == (7, 7)
+            and conv.stride == (2, 2) and conv.padding == (3, 3)
+            and conv.dilation == (1, 1) and conv.groups == 1
+            and conv.bias is None and conv.padding_mode == "zeros"
+            and conv.in_channels == 3 and conv.out_channels == 64):
+        return False
+    # under bf16 autocast fp32 tensors reach the kernel as bf16; the cast
+    # keeps the strides, and the kernel wants both channels_last.  A tensor
+    # that is bf16 already reaches it as it is and must be 16-byte aligned.
+    autocast = (torch.is_autocast_enabled("cuda")
+                and torch.get_autocast_dtype("cuda") == torch.bfloat16)
+    w = conv.weight
+
+    def takes(t):
+        return (t.is_cuda and t.dim() == 4
+                and t.is_contiguous(memory_format=torch.channels_last)
+                and (t.data_ptr() % 16 == 0 if t.dtype == torch.bfloat16
+                     else autocast and t.dtype == torch.float32))
+
+    if not (takes(x) and takes(w) and w.device == x.device
+            and x.shape[1] == 3 and _pool_is_3x3_s2_p1(pool)):
+        return False
+    plan = _C.conv_stem_plan(x.shape[0], x.shape[2], x.shape[3])
+    # the plan's bounds on the output's pixels are the BatchNorm kernels'
+    return (plan["eligible"] and (plan["native"] or mode == "all")
+            and _bn_native(bn))
+
+
+def conv_stem_bn_act_pool(conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d,
+                          x: torch.Tensor, pool: torch.nn.Module
+                          ) -> torch.Tensor:
+    """``pool(relu(bn(conv(x))))`` for the stem: where the native forward
+    runs (``native_conv_stem_mode``), ``bn`` takes its statistics from the
+    partials that come with the output."""
+    if not _conv_stem_native(conv, bn, x, pool):
+        return bn_act_pool(bn, conv(x), pool)
+    y, part = _ConvStem.apply(x, conv.weight, True)
+    return bn_act_pool(bn, y, pool, part=part)
