@@ -15,8 +15,11 @@
 
 #include <cstring>
 #include <functional>
+#include <map>
+#include <mutex>
 #include <thread>
 #include <tuple>
+#include <vector>
 
 #include "backend.h"
 #include "bn_plan.h"
@@ -1372,6 +1375,120 @@ int py_conv3x3_wrw_row(int64_t batch, int64_t h, int64_t w, int64_t c,
   return conv3x3_wrw_row(p, group, t);
 }
 
+// ---- 3x3 convolution backward-weights, ring ---------------------------------
+
+// 256 bytes of zeros on `device` for the zero positions of conv3x3_wrw_ring:
+// allocated at the first call, written once by a blocking copy from the host
+// and kept for the life of the process.
+const void* conv3x3_ring_zeros(int device) {
+  static std::mutex mu;
+  static std::map<int, void*> zeros;
+  std::lock_guard<std::mutex> lock(mu);
+  void*& z = zeros[device];
+  if (z == nullptr) {
+    const std::vector<char> host(256, 0);
+    CGX_HIP_CHECK(hipMalloc(&z, host.size()));
+    CGX_HIP_CHECK(hipMemcpy(z, host.data(), host.size(), hipMemcpyHostToDevice));
+  }
+  return z;
+}
+
+bool py_conv3x3_wrw_ring_eligible(const at::Tensor& dy, const at::Tensor& x) {
+  return py_conv3x3_wrw_eligible(dy, x) &&
+         conv3x3_wrw_ring_plan(x.size(0), x.size(2), x.size(3), x.size(1),
+                               dy.size(1)).eligible;
+}
+
+// as py_conv3x3_wrw, by conv3x3_wrw_ring; `stages` 0 is the plan's own
+at::Tensor py_conv3x3_wrw_ring(const at::Tensor& dy, const at::Tensor& x,
+                               int64_t max_workgroups, int64_t stages) {
+  TORCH_CHECK(max_workgroups >= 0, "conv3x3_wrw_ring: max_workgroups >= 0");
+  TORCH_CHECK(py_conv3x3_wrw_ring_eligible(dy, x),
+              "conv3x3_wrw_ring: dy or x is not eligible");
+  const Conv3x3WrwRingPlan p =
+      conv3x3_wrw_ring_plan(x.size(0), x.size(2), x.size(3), x.size(1),
+                            dy.size(1), max_workgroups, (int)stages);
+  TORCH_CHECK(p.eligible, "conv3x3_wrw_ring: not eligible at these stages");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dy.device().index());
+  auto dw = at::empty({p.n, p.c, 3, 3}, dy.options(),
+                      at::MemoryFormat::ChannelsLast);
+  auto part =
+      at::empty({p.splits, p.n, 9 * p.c}, dy.options().dtype(at::kFloat));
+  launch_conv3x3_wrw_ring(p, dy.data_ptr(), x.data_ptr(),
+                          conv3x3_ring_zeros(dy.device().index()),
+                          part.data_ptr<float>(), dw.data_ptr(),
+                          bn_stream(dy));
+  return dw;
+}
+
+py::dict py_conv3x3_wrw_ring_plan(int64_t batch, int64_t h, int64_t w,
+                                  int64_t c, int64_t n, int64_t max_workgroups,
+                                  int64_t stages) {
+  const Conv3x3WrwRingPlan p =
+      conv3x3_wrw_ring_plan(batch, h, w, c, n, max_workgroups, (int)stages);
+  py::dict d;
+  d["eligible"] = p.eligible;
+  d["native"] = p.native;
+  d["threads"] = kConvThreads;
+  d["bn"] = p.bn;
+  d["bk"] = p.bk;
+  d["ntiles_n"] = p.ntiles_n;
+  d["ntiles_k"] = p.ntiles_k;
+  d["pitch"] = p.pitch;
+  d["images"] = p.images;
+  d["group_rows"] = p.group_rows;
+  d["hr"] = p.hr;
+  d["chunks_per_image"] = p.chunks_per_image;
+  d["chunks"] = p.chunks;
+  d["strip_dy"] = p.strip_dy;
+  d["strip_x"] = p.strip_x;
+  d["stages"] = p.stages;
+  d["dy_glds"] = p.dy_glds;
+  d["x_glds"] = p.x_glds;
+  d["stage_bytes"] = p.stage_bytes;
+  d["splits"] = p.splits;
+  d["grid"] = p.grid;
+  d["chunks_per_split"] = p.chunks_per_split;
+  d["lds_bytes"] = p.lds_bytes;
+  d["lds_budget"] = kConvLdsBytes;
+  d["partial_floats"] = p.partial_floats;
+  return d;
+}
+
+// Test seam: the fill of one stage with `chunk` replayed on the host.  Entry
+// [wave, j, lane] holds (byte of the stage, 1 for the X image, position of
+// the strip, 16-byte vector of the 64 channels, pixel b*H*W + h*W + w that
+// is loaded or -1 for zeros) of the 16 bytes that lane `lane` of instruction
+// j of `wave` moves.
+at::Tensor py_conv3x3_wrw_ring_fill(int64_t batch, int64_t h, int64_t w,
+                                    int64_t c, int64_t n,
+                                    int64_t max_workgroups, int64_t stages,
+                                    int64_t chunk) {
+  const Conv3x3WrwRingPlan p =
+      conv3x3_wrw_ring_plan(batch, h, w, c, n, max_workgroups, (int)stages);
+  TORCH_CHECK(p.eligible, "conv3x3_wrw_ring_fill: shape is not eligible");
+  TORCH_CHECK(chunk >= 0 && chunk < p.chunks, "conv3x3_wrw_ring_fill: chunk");
+  const int waves = kConvThreads / 64, glds = p.dy_glds + p.x_glds;
+  auto out =
+      at::empty({waves, glds, 64, 5}, at::TensorOptions().dtype(at::kLong));
+  int64_t* e = out.data_ptr<int64_t>();
+  const Conv3x3RingWindow win = conv3x3_wrw_ring_window(p, (int)chunk);
+  for (int wave = 0; wave < waves; wave++)
+    for (int j = 0; j < glds; j++)
+      for (int lane = 0; lane < 64; lane++, e += 5) {
+        const Conv3x3RingSlot s = conv3x3_wrw_ring_slot(p, wave, j, lane);
+        const Conv3x3RingSrc src = conv3x3_wrw_ring_src(p, s.is_x, s.pos);
+        const bool live =
+            (unsigned)(src.key - win.first) < (unsigned)win.count;
+        e[0] = (4 * j + wave) * 1024 + 16 * lane;
+        e[1] = s.is_x;
+        e[2] = s.pos;
+        e[3] = s.vec;
+        e[4] = live ? (int64_t)win.pixel + src.pixel : -1;
+      }
+  return out;
+}
+
 // ---- 3x3 convolution forward with statistics --------------------------------
 
 Conv3x3FwdPlan conv3x3_fwd_plan_of(const at::Tensor& x, const at::Tensor& w,
@@ -2113,6 +2230,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("max_workgroups"), py::arg("group"), py::arg("t"),
         "Test seam: the tensor row b*H + h that row t of a group of images "
         "is, or -1 for a zero row.");
+  m.def("conv3x3_wrw_ring", &cgx::py_conv3x3_wrw_ring, py::arg("dy"),
+        py::arg("x"), py::arg("max_workgroups") = 0, py::arg("stages") = 0,
+        "conv3x3_wrw through a ring of LDS stages filled by loads direct to "
+        "LDS; the same bits where the two plans agree on tile, hr, images "
+        "and splits.  stages: 0 the plan's own, 2 or 3.");
+  m.def("conv3x3_wrw_ring_eligible", &cgx::py_conv3x3_wrw_ring_eligible,
+        py::arg("dy"), py::arg("x"),
+        "True where conv3x3_wrw_ring takes (dy, x).");
+  m.def("conv3x3_wrw_ring_plan", &cgx::py_conv3x3_wrw_ring_plan,
+        py::arg("batch"), py::arg("h"), py::arg("w"), py::arg("c"),
+        py::arg("n"), py::arg("max_workgroups") = 0, py::arg("stages") = 0,
+        "The launch geometry of conv3x3_wrw_ring, and `native`: whether the "
+        "model uses it for this problem.");
+  m.def("conv3x3_wrw_ring_fill", &cgx::py_conv3x3_wrw_ring_fill,
+        py::arg("batch"), py::arg("h"), py::arg("w"), py::arg("c"),
+        py::arg("n"), py::arg("max_workgroups"), py::arg("stages"),
+        py::arg("chunk"),
+        "Test seam: [waves, instructions, 64, 5] int64, (stage byte, is X, "
+        "strip position, vector, pixel or -1) of every 16 bytes of the fill "
+        "of one stage with `chunk`.");
   m.def("conv3x3_stats", &cgx::py_conv3x3_stats, py::arg("x"),
         py::arg("weight"), py::arg("max_workgroups") = 0,
         "conv2d(x, weight, padding=1) of a 3x3 / stride 1 convolution by the "

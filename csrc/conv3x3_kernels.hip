@@ -49,6 +49,8 @@
 // once: no atomics, the same bits every run.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "bn_moments.h"
 #include "check.h"
 #include "conv3x3_plan.h"
@@ -220,6 +222,253 @@ void launch_wrw3x3(const Conv3x3WrwPlan& p, const void* dy, const void* x,
   hipLaunchKernelGGL((conv3x3_wrw<BN, BK>), dim3(p.grid), dim3(kT),
                      p.lds_bytes, stream, static_cast<const uint4*>(dy),
                      static_cast<const uint4*>(x), part, p);
+  CGX_HIP_CHECK(hipGetLastError());
+}
+
+// ---- weight gradient through a ring of LDS stages -----------------------------
+//
+// conv3x3_wrw with the chunks loaded straight into LDS (plan:
+// conv3x3_wrw_ring_plan), as conv1x1_wrw_ring does it for the 1x1 weight
+// gradient: the same images, read addresses and MFMA order, so the same bits
+// at the same tile, hr, images and splits.  Per chunk:
+//
+//   s_waitcnt vmcnt(N)   the oldest stage of this wave has landed; N counts
+//                        the instructions of the younger ones
+//   s_barrier            ... and that of every wave
+//   ds_read_b64_tr_b16, MFMAs
+//   s_waitcnt lgkmcnt(0), s_barrier   every wave has read the stage
+//   global_load_lds      chunk t + stages into the stage just freed
+//
+// Zeros.  Which position of a strip holds which pixel does not depend on the
+// chunk, only whether it is live does (conv3x3_wrw_ring_src / _window): a
+// lane keeps, per instruction, the byte offset of its 16 bytes from the
+// chunk's first pixel and the key, and points a load whose key the chunk does
+// not admit at `zeros`.  Every byte of a stage is written on every chunk and
+// nothing outside the two tensors and `zeros` is read.
+//
+// Operand reads.  The compiler would put s_waitcnt vmcnt(0) in front of
+// every LDS read it knows of while a global_load_lds is pending, so the reads
+// are instructions of the kernel's own (ring_read_tr) and the kernel counts
+// lgkmcnt itself.  A step has 20 reads and the counter ends at 15, so the
+// reads run kRingAhead taps ahead of the MFMAs, not a step: before the MFMA
+// of tap t the reads of tap t + kRingAhead are issued, of the next step
+// where that is past tap 8 (with its A operand at tap 0), and the wait
+// leaves exactly those in flight.  Nothing but source order and the
+// sched_barrier(0) after each wait keeps the MFMAs behind the waits: after a
+// change of toolchain read the .s again.
+
+typedef __attribute__((address_space(3))) char lds_char;
+typedef __attribute__((address_space(1))) const void global_cvoid;
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+constexpr int kRingAhead = 6;
+static_assert(2 * kRingAhead + 2 <= 15 && kRingAhead < 9);
+
+template <int N>
+__device__ __forceinline__ void ring_wait_lgkmcnt() {
+  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
+}
+// s_waitcnt vmcnt(n) for a uniform n <= N
+template <int N>
+__device__ __forceinline__ void ring_wait_vmcnt(int n) {
+  if (n >= N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+  else if constexpr (N > 0) ring_wait_vmcnt<N - 1>(n);
+}
+template <int OFF>
+__device__ __forceinline__ u32x2 ring_read_tr(unsigned addr) {
+  static_assert(OFF >= 0 && OFF < 65536);
+  u32x2 v;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2"
+               : "=v"(v)
+               : "v"(addr), "n"(OFF));
+  return v;
+}
+// rows +0 .. +3 in elements 0 .. 3, rows +4 .. +7 in elements 4 .. 7
+__device__ __forceinline__ bf16x8 ring_pair(const u32x2 (&v)[2]) {
+  const unsigned w __attribute__((ext_vector_type(4))) = {v[0][0], v[0][1],
+                                                          v[1][0], v[1][1]};
+  return __builtin_bit_cast(bf16x8, w);
+}
+template <int I, int N, class F>
+__device__ __forceinline__ void ring_for(F&& f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    ring_for<I + 1, N>(f);
+  }
+}
+
+__global__ __launch_bounds__(kT) void conv3x3_wrw_ring(
+    const uint4* __restrict__ dy, const uint4* __restrict__ x,
+    const uint4* __restrict__ zeros, float* __restrict__ part,
+    Conv3x3WrwRingPlan p) {
+  extern __shared__ uint4 lds[];
+  constexpr int C = 64;                  // both images
+  constexpr int kStep = 16 * 2 * C;      // bytes of a 16-position step
+  constexpr int kHi = 4 * 2 * C;         // ... and to an operand's second read
+  constexpr int G = kConv3x3RingMaxGlds;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int c = lane & 31, h = lane >> 5;
+  const int wn = wave >> 1, wk = wave & 1;
+  const int tile = conv3x3_wrw_tile(p, blockIdx.x);
+  const int split = conv3x3_wrw_split(p, blockIdx.x);
+  const int n0 = (tile / p.ntiles_k) * C, k0 = (tile % p.ntiles_k) * C;
+
+  // as conv3x3_wrw, from the start of a stage
+  const int q = (lane >> 2) & 3;
+  const int in_cell = 32 * ((lane >> 4) & 1) + 8 * (lane & 3);
+  const int img_k = p.dy_glds * 4096;
+  const unsigned an = wrw_cell<C>(8 * h + q, wn) + in_cell;
+  unsigned ak[9];
+#pragma unroll
+  for (int tap = 0; tap < 9; tap++)
+    ak[tap] = img_k +
+              wrw_cell<C>(8 * h + q + (tap / 3) * p.pitch + tap % 3, wk) +
+              in_cell;
+
+  f32x16 acc[9];
+#pragma unroll
+  for (int tap = 0; tap < 9; tap++)
+#pragma unroll
+    for (int e = 0; e < 16; e++) acc[tap][e] = 0.f;
+
+  // the lane's 16 bytes of instruction j of a stage: see above
+  const int glds = p.dy_glds + p.x_glds;
+  int off[G], key[G];
+#pragma unroll
+  for (int j = 0; j < G; j++) {
+    off[j] = 0, key[j] = kConv3x3RingNever;
+    if (j < glds) {  // uniform
+      const Conv3x3RingSlot s = conv3x3_wrw_ring_slot(p, wave, j, lane);
+      const Conv3x3RingSrc src = conv3x3_wrw_ring_src(p, s.is_x, s.pos);
+      off[j] = (src.pixel * (s.is_x ? p.c : p.n) + s.vec * 8) * 2;
+      key[j] = src.key;
+    }
+  }
+
+  // the chunks split, split + splits, ... below p.chunks
+  const int T = (p.chunks - split + p.splits - 1) / p.splits;
+  const char* dy_b = reinterpret_cast<const char*>(dy) + n0 * 2;
+  const char* x_b = reinterpret_cast<const char*>(x) + k0 * 2;
+  auto issue = [&](int t, int slot) __attribute__((always_inline)) {
+    const Conv3x3RingWindow win =
+        conv3x3_wrw_ring_window(p, split + t * p.splits);
+    const char* src_n = dy_b + (int64_t)win.pixel * p.n * 2;
+    const char* src_k = x_b + (int64_t)win.pixel * p.c * 2;
+    lds_char* dst =
+        (lds_char*)reinterpret_cast<char*>(lds) + slot * p.stage_bytes +
+        wave * 1024;
+#pragma unroll
+    for (int j = 0; j < G; j++)
+      if (j < glds) {  // uniform
+        const bool live = (unsigned)(key[j] - win.first) < (unsigned)win.count;
+        const char* src = (j < p.dy_glds ? src_n : src_k) + off[j];
+        __builtin_amdgcn_global_load_lds(
+            (global_cvoid*)(live ? src : reinterpret_cast<const char*>(zeros)),
+            dst + j * 4096, 16, 0, 0);
+      }
+  };
+
+  // The 16-position steps of the stage at LDS address `stage`.
+  const int steps_n = p.strip_dy / 16;
+  auto steps = [&](unsigned stage) __attribute__((always_inline)) {
+    u32x2 a[2][2], b[2][9][2];
+    unsigned pa = stage + an, pb[9];
+#pragma unroll
+    for (int tap = 0; tap < 9; tap++) pb[tap] = stage + ak[tap];
+    // the reads of tap TAP of this step (NEXT 0) or the one after it, into
+    // register set SET
+    auto read = [&](auto set_, auto tap_, auto next_)
+                    __attribute__((always_inline)) {
+      constexpr int SET = decltype(set_)::value, TAP = decltype(tap_)::value;
+      constexpr int O = decltype(next_)::value * kStep;
+      if constexpr (TAP == 0) {
+        a[SET][0] = ring_read_tr<O>(pa);
+        a[SET][1] = ring_read_tr<O + kHi>(pa);
+      }
+      b[SET][TAP][0] = ring_read_tr<O>(pb[TAP]);
+      b[SET][TAP][1] = ring_read_tr<O + kHi>(pb[TAP]);
+    };
+    // one step from register set SET; LAST: no step follows
+    auto step = [&](auto set_, auto last_) __attribute__((always_inline)) {
+      constexpr int SET = decltype(set_)::value;
+      constexpr bool LAST = decltype(last_)::value;
+      ring_for<0, 9>([&](auto tap_) __attribute__((always_inline)) {
+        constexpr int TAP = decltype(tap_)::value, AHEAD = TAP + kRingAhead;
+        if constexpr (AHEAD < 9) {
+          read(set_, std::integral_constant<int, AHEAD>{},
+               std::integral_constant<int, 0>{});
+          ring_wait_lgkmcnt<2 * kRingAhead>();
+        } else if constexpr (!LAST) {
+          read(std::integral_constant<int, SET ^ 1>{},
+               std::integral_constant<int, AHEAD - 9>{},
+               std::integral_constant<int, 1>{});
+          ring_wait_lgkmcnt<2 * kRingAhead + 2>();  // with the A operand
+        } else {
+          ring_wait_lgkmcnt<2 * (8 - TAP)>();
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        acc[TAP] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            ring_pair(a[SET]), ring_pair(b[SET][TAP]), acc[TAP], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      });
+      pa += kStep;
+#pragma unroll
+      for (int tap = 0; tap < 9; tap++) pb[tap] += kStep;
+    };
+    ring_for<0, kRingAhead>([&](auto tap_) __attribute__((always_inline)) {
+      read(std::integral_constant<int, 0>{}, tap_,
+           std::integral_constant<int, 0>{});
+    });
+    // an even count (the plan's strip_dy): one path, so that no accumulator
+    // is copied where two would meet
+    for (int s = 2; s < steps_n; s += 2) {
+      step(std::integral_constant<int, 0>{}, std::false_type{});
+      step(std::integral_constant<int, 1>{}, std::false_type{});
+    }
+    step(std::integral_constant<int, 0>{}, std::false_type{});
+    step(std::integral_constant<int, 1>{}, std::true_type{});
+  };
+
+  for (int s = 0; s < p.stages; s++)
+    if (s < T) issue(s, s);
+  const unsigned ring_addr =
+      (unsigned)(unsigned long)(lds_char*)reinterpret_cast<char*>(lds);
+  int slot = 0;
+  for (int t = 0; t < T; t++) {
+    const int younger = T - 1 - t < p.stages - 1 ? T - 1 - t : p.stages - 1;
+    ring_wait_vmcnt<2 * G>(younger * glds);
+    __builtin_amdgcn_s_barrier();
+    steps(ring_addr + slot * p.stage_bytes);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    if (t + p.stages < T) issue(t + p.stages, slot);
+    slot = slot + 1 == p.stages ? 0 : slot + 1;
+  }
+
+  // as conv3x3_wrw
+  const int64_t ld = 9 * (int64_t)p.c;
+  float* out = part + (int64_t)split * p.n * ld;
+#pragma unroll
+  for (int tap = 0; tap < 9; tap++)
+#pragma unroll
+    for (int e = 0; e < 16; e++) {
+      const int n = n0 + wn * 32 + acc_row(e, h);
+      const int k = k0 + wk * 32 + c;
+      out[n * ld + tap * p.c + k] = acc[tap][e];
+    }
+}
+
+void launch_wrw3x3_ring(const Conv3x3WrwRingPlan& p, const void* dy,
+                        const void* x, const void* zeros, float* part,
+                        hipStream_t stream) {
+  static const hipError_t attr = hipFuncSetAttribute(
+      reinterpret_cast<const void*>(&conv3x3_wrw_ring),
+      hipFuncAttributeMaxDynamicSharedMemorySize, kConvLdsBytes);
+  CGX_HIP_CHECK(attr);
+  hipLaunchKernelGGL(conv3x3_wrw_ring, dim3(p.grid), dim3(kT), p.lds_bytes,
+                     stream, static_cast<const uint4*>(dy),
+                     static_cast<const uint4*>(x),
+                     static_cast<const uint4*>(zeros), part, p);
   CGX_HIP_CHECK(hipGetLastError());
 }
 
@@ -728,6 +977,23 @@ void launch_conv3x3_wrw(const Conv3x3WrwPlan& p, const void* dy, const void* x,
                   p.splits <= p.chunks,
               "conv3x3_wrw: plan and kernel disagree");
   launch_wrw3x3<64, 64>(p, dy, x, part, stream);
+  launch_wrw_finalize(part, dw, p.splits, (int64_t)p.n * 9 * p.c, stream);
+}
+
+void launch_conv3x3_wrw_ring(const Conv3x3WrwRingPlan& p, const void* dy,
+                             const void* x, const void* zeros, float* part,
+                             void* dw, hipStream_t stream) {
+  TORCH_CHECK(p.eligible, "conv3x3_wrw_ring: shape is not eligible");
+  const int glds = p.dy_glds + p.x_glds;
+  TORCH_CHECK(p.bn == 64 && p.bk == 64 && p.stages >= 2 && p.stages <= 3 &&
+                  glds <= kConv3x3RingMaxGlds &&
+                  p.strip_dy <= 32 * p.dy_glds && p.strip_x <= 32 * p.x_glds &&
+                  p.strip_dy % 32 == 0 && p.stage_bytes == glds * 4096 &&
+                  p.lds_bytes == p.stages * p.stage_bytes &&
+                  p.lds_bytes <= kConvLdsBytes && p.splits <= p.chunks &&
+                  zeros != nullptr,
+              "conv3x3_wrw_ring: plan and kernel disagree");
+  launch_wrw3x3_ring(p, dy, x, zeros, part, stream);
   launch_wrw_finalize(part, dw, p.splits, (int64_t)p.n * 9 * p.c, stream);
 }
 

@@ -22,6 +22,17 @@ constexpr Measured3x3 kNativeWrw3x3[] = {
     {256, 28, 28, 128, 128},
 };
 
+// The same rule for conv3x3_wrw_ring plus the finalize against the path the
+// problem takes without it: conv3x3_wrw where the table above has it, the
+// stock path elsewhere (benchmarks/conv3x3_wrw_ring_shapes.py).  All four met
+// it, in two processes, with two stages and with three.
+constexpr Measured3x3 kNativeWrw3x3Ring[] = {
+    {256, 56, 56, 64, 64},
+    {256, 28, 28, 128, 128},
+    {256, 14, 14, 256, 256},
+    {256, 7, 7, 512, 512},
+};
+
 // The same rule for conv3x3_stats followed by bn_act_forward with its partials
 // against MIOpen's forward followed by bn_act_forward with a statistics pass
 // (benchmarks/conv3x3_fwd_shapes.py).  All four bottleneck problems of
@@ -138,6 +149,82 @@ Conv3x3WrwPlan conv3x3_wrw_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
   p.strip_dy = strip_dy_of(p.hr, p.pitch);
   p.strip_x = strip_x_of(p.hr, p.pitch);
   p.lds_bytes = (p.strip_dy * p.bn + p.strip_x * p.bk) * 2;
+  p.partial_floats = (int64_t)p.splits * p.n * 9 * p.c;
+  p.magic_pitch = magic_of(p.pitch);
+  p.magic_h1 = magic_of(p.h + 1);
+  return p;
+}
+
+namespace {
+
+int ring_glds(int strip) { return (strip + 31) / 32; }
+// The ring's dY strip is whole rounds of the fill, which costs no LDS and
+// makes the number of 16-position steps even (the kernel alternates two sets
+// of operand registers and has one path through a chunk) ...
+int ring_strip_dy_of(int rows, int pitch) { return round_up(rows * pitch, 32); }
+// ... and its X strip what that reaches
+int ring_strip_x_of(int rows, int pitch) {
+  return round_up(ring_strip_dy_of(rows, pitch) + 2 * pitch + 2, 4);
+}
+
+// whether chunks of `rows` rows fit a stage of a ring of `stages`
+bool ring_fits(int rows, int pitch, int stages) {
+  const int glds = ring_glds(ring_strip_dy_of(rows, pitch)) +
+                   ring_glds(ring_strip_x_of(rows, pitch));
+  return glds <= kConv3x3RingMaxGlds &&
+         glds * 4096 * stages <= kConvLdsBytes;
+}
+
+}  // namespace
+
+Conv3x3WrwRingPlan conv3x3_wrw_ring_plan(int64_t batch, int64_t h, int64_t w,
+                                         int64_t c, int64_t n,
+                                         int64_t max_workgroups, int stages) {
+  Conv3x3WrwRingPlan p;
+  p.bn = p.bk = 64;
+  p.stages = stages == 0 ? kConv3x3RingStages : stages;
+  p.eligible = (p.stages == 2 || p.stages == 3) && pow2_in(c, 64, 512) &&
+               pow2_in(n, 64, 512) && batch >= 1 && h >= 1 && w >= 1 &&
+               batch <= kBnMaxRows && h <= kBnMaxRows && w <= kBnMaxRows &&
+               batch * h * w <= kBnMaxRows &&
+               ring_fits(1, (int)w + 1, p.stages);
+  if (!p.eligible) return p;
+  p.batch = (int)batch, p.h = (int)h, p.w = (int)w, p.c = (int)c, p.n = (int)n;
+  for (const Measured3x3& m : kNativeWrw3x3Ring)
+    p.native |= m.batch == batch && m.h == h && m.w == w && m.c == c && m.n == n;
+  p.pitch = p.w + 1;
+  p.ntiles_n = p.n / p.bn;
+  p.ntiles_k = p.c / p.bk;
+  const int tiles = p.ntiles_n * p.ntiles_k;
+
+  // conv3x3_wrw_plan's splits: one workgroup per CU, the partials within the
+  // bytes of the operands, no more splits than chunks
+  const int64_t rows = batch * h * w;
+  const int64_t operand_bytes =
+      2 * rows * (n * p.ntiles_k + c * p.ntiles_n);
+  const int64_t by_bytes = std::max<int64_t>(1, operand_bytes / (72 * n * c));
+  int64_t splits = std::min<int64_t>(by_bytes, std::max(1, kConvCus / tiles));
+  if (max_workgroups > 0)
+    splits = std::min(splits, std::max<int64_t>(
+                                  1, std::min<int64_t>(max_workgroups, 1 << 20) /
+                                         tiles));
+  int limit = 1;
+  while (ring_fits(limit + 1, p.pitch, p.stages) &&
+         limit + 1 <= (int)std::min<int64_t>(batch * (h + 1), 1 << 10))
+    limit++;
+  set_chunks(p, limit);
+  splits = std::min<int64_t>(splits, p.chunks);
+  if (splits > 8) splits -= splits % 8;  // conv3x3_wrw_split
+  p.splits = (int)splits;
+  p.grid = tiles * p.splits;
+  p.chunks_per_split = (p.chunks + p.splits - 1) / p.splits;
+
+  p.strip_dy = ring_strip_dy_of(p.hr, p.pitch);
+  p.strip_x = ring_strip_x_of(p.hr, p.pitch);
+  p.dy_glds = ring_glds(p.strip_dy);
+  p.x_glds = ring_glds(p.strip_x);
+  p.stage_bytes = (p.dy_glds + p.x_glds) * 4096;
+  p.lds_bytes = p.stages * p.stage_bytes;
   p.partial_floats = (int64_t)p.splits * p.n * 9 * p.c;
   p.magic_pitch = magic_of(p.pitch);
   p.magic_h1 = magic_of(p.h + 1);

@@ -102,6 +102,98 @@ __host__ __device__ inline int conv3x3_wrw_row(const Conv3x3WrwPlan& p,
 void launch_conv3x3_wrw(const Conv3x3WrwPlan& p, const void* dy, const void* x,
                         float* part, void* dw, hipStream_t stream);
 
+// ---- weight gradient through a ring of LDS stages (conv3x3_wrw_ring) ----------
+//
+// conv3x3_wrw with the chunks loaded straight into LDS, as conv1x1_wrw_ring:
+// no staging registers, `stages` chunks in flight across the barriers.  The
+// strips, the images, the walk and the partials are those above, so equal
+// (tile, hr, images, splits) give equal bits.  A stage holds the dY image and
+// behind it the X image, each rounded up to whole rounds of the four waves'
+// global_load_lds_dwordx4 (4 KiB, 32 positions of a 64-channel image); the
+// positions past a strip load zeros.  The stages share LDS, so a chunk is
+// shorter than conv3x3_wrw's: at most 80 KiB with two stages, 52 KiB with
+// three.  `native` is the ring's own measurement against the path the problem
+// takes without it.
+constexpr int kConv3x3RingStages = 2;  // the geometry kept (RESULTS.md)
+// instructions of a wave per stage, both images: the registers that hold
+// their source offsets, and 80 KiB
+constexpr int kConv3x3RingMaxGlds = 20;
+
+struct Conv3x3WrwRingPlan : Conv3x3WrwPlan {
+  int stages = 0;
+  int dy_glds = 0, x_glds = 0;  // instructions of a wave per stage and image
+  int stage_bytes = 0;  // (dy_glds + x_glds) * 4096; lds_bytes = stages * it
+};
+
+// `stages` 0 is kConv3x3RingStages; 2 and 3 are built.
+Conv3x3WrwRingPlan conv3x3_wrw_ring_plan(int64_t batch, int64_t h, int64_t w,
+                                         int64_t c, int64_t n,
+                                         int64_t max_workgroups = 0,
+                                         int stages = 0);
+
+// One global_load_lds_dwordx4 of a wave writes 1 KiB of LDS, lane l the 16
+// bytes at 16*l.  Instruction j of `wave` fills bytes (4j + wave) * 1024 ..
+// of the stage, dY's image first (j < dy_glds), so the wrw_cell permutation
+// goes onto the address a lane loads from: position `pos` of the strip and
+// 16-byte vector `vec` of its 64 channels are what the image holds at the
+// lane's bytes.
+struct Conv3x3RingSlot {
+  bool is_x;
+  int pos, vec;
+};
+__host__ __device__ inline Conv3x3RingSlot conv3x3_wrw_ring_slot(
+    const Conv3x3WrwRingPlan& p, int wave, int j, int lane) {
+  const bool is_x = j >= p.dy_glds;
+  const WrwImageSlot s = conv1x1_wrw_image_slot(
+      64, conv1x1_wrw_ring_piece(wave, is_x ? j - p.dy_glds : j) + 16 * lane);
+  return {is_x, s.row, s.channel / 8};
+}
+
+// What position `pos` of a strip loads, whatever the chunk: the pixel
+// relative to the chunk's first (conv3x3_wrw_ring_window) and a key that the
+// chunk's window admits or not.  With one image per group the key is the row
+// relative to the chunk's first, with several the image of the group.  A
+// position that is zero on every chunk (pad column, rows past the chunk, the
+// tail of the strip and of the stage, column 0 of X, the row between two
+// images) has a key that no window admits.
+constexpr int kConv3x3RingNever = -(1 << 20);
+struct Conv3x3RingSrc {
+  int pixel, key;
+};
+__host__ __device__ inline Conv3x3RingSrc conv3x3_wrw_ring_src(
+    const Conv3x3WrwRingPlan& p, bool is_x, int pos) {
+  const int x1 = is_x ? 1 : 0;
+  const int rr = (int)(((unsigned)pos * p.magic_pitch) >> kConv3x3MagicShift);
+  const int col = pos - rr * p.pitch - x1, t = rr - x1;
+  if (pos >= (is_x ? p.strip_x : p.strip_dy) || rr >= p.hr + 2 * x1 ||
+      col < 0 || col >= p.w)
+    return {0, kConv3x3RingNever};
+  if (p.images == 1) return {t * p.w + col, t};
+  if (t < 0 || t >= p.group_rows) return {0, kConv3x3RingNever};
+  const int image = (int)(((unsigned)t * p.magic_h1) >> kConv3x3MagicShift);
+  const int h = t - image * (p.h + 1);
+  if (h >= p.h) return {0, kConv3x3RingNever};
+  return {(image * p.h + h) * p.w + col, image};
+}
+// The chunk's first pixel and the keys it admits: first <= key < first + count.
+struct Conv3x3RingWindow {
+  int pixel, first, count;
+};
+__host__ __device__ inline Conv3x3RingWindow conv3x3_wrw_ring_window(
+    const Conv3x3WrwRingPlan& p, int chunk) {
+  const int group = chunk / p.chunks_per_image;
+  if (p.images > 1)
+    return {group * p.images * p.h * p.w, 0, p.batch - group * p.images};
+  const int t0 = (chunk - group * p.chunks_per_image) * p.hr;
+  return {(group * p.h + t0) * p.w, -t0, p.h};
+}
+
+// As launch_conv3x3_wrw.  `zeros` is at least 16 bytes of zeros on the
+// device, which the lanes of the zero positions load.
+void launch_conv3x3_wrw_ring(const Conv3x3WrwRingPlan& p, const void* dy,
+                             const void* x, const void* zeros, float* part,
+                             void* dw, hipStream_t stream);
+
 // ---- forward with BatchNorm partials (conv3x3_stats) -------------------------
 //
 // Y[R, N] = sum over the nine taps t of X_t[R, C] * W_t[N, C]^T, R = B*H*W the

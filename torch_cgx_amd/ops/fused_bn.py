@@ -447,8 +447,9 @@ class _Conv3x3(torch.autograd.Function):
     """``(y, part) = f(x, weight)``: ``conv2d(x, weight, padding=1)``, by the
     native implicit GEMM with the BatchNorm partials of ``y``
     (``_C.conv3x3_stats``) where ``native_fwd`` says so, else stock with
-    ``part`` None.  With ``native_wrw`` the weight gradient comes from the
-    native implicit GEMM (``_C.conv3x3_wrw``) and with ``native_bwd`` the
+    ``part`` None.  The weight gradient comes from ``_C.conv3x3_wrw_ring``
+    where its switch and table have the problem, else with ``native_wrw`` from
+    the native implicit GEMM (``_C.conv3x3_wrw``), and with ``native_bwd`` the
     input gradient from ``_C.conv3x3_bwd_data``, each where it takes the
     gradient that arrives; the stock backward computes what remains."""
 
@@ -470,6 +471,8 @@ class _Conv3x3(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         need_dx, need_dw = ctx.needs_input_grad[:2]
         dx = dw = None
+        if need_dw and _conv3x3_wrw_ring_takes(dy, x):
+            dw, need_dw = _C.conv3x3_wrw_ring(dy, x), False
         if need_dw and ctx.native_wrw and _C.conv3x3_wrw_eligible(dy, x):
             dw, need_dw = _C.conv3x3_wrw(dy, x), False
         if (need_dx and ctx.native_bwd
@@ -482,6 +485,25 @@ class _Conv3x3(torch.autograd.Function):
             dx = dx_stock if need_dx else dx
             dw = dw_stock if need_dw else dw
         return dx, dw, None, None, None
+
+
+def native_conv3x3_wrw_ring_mode() -> str:
+    """``CGX_NATIVE_CONV3X3_WRW_RING``, the switch of the weight gradient
+    through a ring of LDS stages (``_C.conv3x3_wrw_ring``): "0" off, "all"
+    every eligible problem, else ("1", the default) the problems its plan has
+    measured faster than the path they take without it.  Off where
+    ``CGX_FUSED_BN`` is."""
+    if not fused_bn_enabled():
+        return "0"
+    return os.environ.get("CGX_NATIVE_CONV3X3_WRW_RING", "1")
+
+
+def _conv3x3_wrw_ring_takes(dy, x) -> bool:
+    mode = native_conv3x3_wrw_ring_mode()
+    if mode == "0" or not _C.conv3x3_wrw_ring_eligible(dy, x):
+        return False
+    return mode == "all" or _C.conv3x3_wrw_ring_plan(
+        x.shape[0], x.shape[2], x.shape[3], x.shape[1], dy.shape[1])["native"]
 
 
 def native_conv3x3_wrw_mode() -> str:
