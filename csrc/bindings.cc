@@ -1688,6 +1688,80 @@ at::Tensor py_conv_stem_taps(int64_t batch, int64_t h, int64_t w, int64_t row0,
   return out;
 }
 
+// ---- stem convolution weight gradient ------------------------------------------
+
+// dy [B, 64, H/2, W/2] and x [B, 3, H, W] as the BatchNorm kernels take them
+bool py_conv_stem_wrw_eligible(const at::Tensor& dy, const at::Tensor& x) {
+  return bn_tensor_ok(dy) && bn_tensor_ok(x) && x.device() == dy.device() &&
+         x.size(1) == kConvStemC && dy.size(1) == kConvStemN &&
+         x.size(0) == dy.size(0) && x.size(2) == 2 * dy.size(2) &&
+         x.size(3) == 2 * dy.size(3) &&
+         conv_stem_wrw_plan(x.size(0), x.size(2), x.size(3)).eligible;
+}
+
+// Gradient of conv2d(x, weight, stride=2, padding=3) for the [64, 3, 7, 7]
+// weight: (dy, x) -> dw
+at::Tensor py_conv_stem_wrw(const at::Tensor& dy, const at::Tensor& x,
+                            int64_t max_workgroups) {
+  TORCH_CHECK(max_workgroups >= 0, "conv_stem_wrw: max_workgroups >= 0");
+  TORCH_CHECK(py_conv_stem_wrw_eligible(dy, x),
+              "conv_stem_wrw: dy or x is not eligible");
+  const ConvStemWrwPlan p =
+      conv_stem_wrw_plan(x.size(0), x.size(2), x.size(3), max_workgroups);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dy.device().index());
+  // the layout the stock weight gradient of a channels_last model has:
+  // memory [64][7][7][3], the kernel's columns 21r + 3s + c
+  auto dw = at::empty({kConvStemN, kConvStemC, kConvStemTaps, kConvStemTaps},
+                      dy.options(), at::MemoryFormat::ChannelsLast);
+  auto part = at::empty({p.splits, kConvStemN, kConvStemWrwCols},
+                        dy.options().dtype(at::kFloat));
+  launch_conv_stem_wrw(p, dy.data_ptr(), x.data_ptr(), part.data_ptr<float>(),
+                       dw.data_ptr(), bn_stream(dy));
+  return dw;
+}
+
+py::dict py_conv_stem_wrw_plan(int64_t batch, int64_t h, int64_t w,
+                               int64_t max_workgroups) {
+  const ConvStemWrwPlan p = conv_stem_wrw_plan(batch, h, w, max_workgroups);
+  py::dict d;
+  d["eligible"] = p.eligible;
+  d["native"] = p.native;
+  d["threads"] = kConvThreads;
+  d["max_w"] = kConvStemWrwMaxW;
+  d["band_rows"] = p.band_rows;
+  d["bands_per_image"] = p.bands_per_image;
+  d["bands"] = p.bands;
+  d["in_rows"] = p.in_rows;
+  d["dyvecs"] = p.dyvecs;
+  d["xunits"] = p.xunits;
+  d["groups"] = p.groups;
+  d["steps"] = p.steps;
+  d["last_groups"] = p.last_groups;
+  d["last_steps"] = p.last_steps;
+  d["splits"] = p.splits;
+  d["grid"] = p.grid;
+  d["bands_per_split"] = p.bands_per_split;
+  d["buf_bytes"] = p.buf_bytes;
+  d["lds_bytes"] = p.lds_bytes;
+  d["lds_budget"] = kConvLdsBytes;
+  d["partial_floats"] = p.partial_floats;
+  return d;
+}
+
+// Test seam: [splits, 2] int64, the first band and the end of the run of
+// bands that each workgroup of conv_stem_wrw walks.
+at::Tensor py_conv_stem_wrw_walk(int64_t batch, int64_t h, int64_t w,
+                                 int64_t max_workgroups) {
+  const ConvStemWrwPlan p = conv_stem_wrw_plan(batch, h, w, max_workgroups);
+  TORCH_CHECK(p.eligible, "conv_stem_wrw_walk: shape is not eligible");
+  auto out = at::empty({p.splits, 2}, at::TensorOptions().dtype(at::kLong));
+  for (int s = 0; s < p.splits; s++) {
+    out.data_ptr<int64_t>()[2 * s] = conv_stem_wrw_first(p, s);
+    out.data_ptr<int64_t>()[2 * s + 1] = conv_stem_wrw_end(p, s);
+  }
+  return out;
+}
+
 // ---- 3x3 convolution input gradient -------------------------------------------
 
 Conv3x3FwdPlan conv3x3_bwd_plan_of(const at::Tensor& dy, const at::Tensor& w,
@@ -2316,6 +2390,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Test seam: [row1 - row0, 176] int64, the element of x each position "
         "of the padded filter meets for the output pixels row0 .. row1-1, "
         "read through the band's strip; -1 where it is zero or cleared.");
+  m.def("conv_stem_wrw", &cgx::py_conv_stem_wrw, py::arg("dy"), py::arg("x"),
+        py::arg("max_workgroups") = 0,
+        "Weight gradient of the 3 -> 64 channel 7x7 stride-2 stem by the "
+        "native implicit GEMM: (dy, x) -> dw [64, 3, 7, 7] bf16 "
+        "channels_last, every sum in a fixed order.  max_workgroups > 0 caps "
+        "the grid.");
+  m.def("conv_stem_wrw_eligible", &cgx::py_conv_stem_wrw_eligible,
+        py::arg("dy"), py::arg("x"),
+        "True where conv_stem_wrw takes (dy, x): CUDA, bf16, dense "
+        "channels_last and 16-byte aligned, x [B, 3, H, W] with H even and W "
+        "a multiple of 16 up to 752, dy [B, 64, H/2, W/2].");
+  m.def("conv_stem_wrw_plan", &cgx::py_conv_stem_wrw_plan, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("max_workgroups") = 0,
+        "The launch geometry of conv_stem_wrw, and `native`: whether the "
+        "model uses it for this problem.");
+  m.def("conv_stem_wrw_walk", &cgx::py_conv_stem_wrw_walk, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("max_workgroups") = 0,
+        "Test seam: [splits, 2] int64, (first, end) of the bands each "
+        "workgroup of conv_stem_wrw walks.");
   m.def("bn_act2_backward", &cgx::py_bn_act2_backward,
         "Backward of bn_act2_forward: (dy, x3, xd, mean3, invstd3, weight3, "
         "meand, invstdd, weightd, mask) -> (dx3, dxd, dgamma3, dbeta3, "

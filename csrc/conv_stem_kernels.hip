@@ -1,7 +1,8 @@
 // The stem of a ResNet, Conv2d(3, 64, 7, stride 2, padding 3) on channels_last
 // bf16 tensors, as an implicit GEMM built for three input channels, which also
 // produces the BatchNorm partials of its output as conv3x3_stats does
-// (conv_stem_stats).  Geometry: conv_stem_plan.h.
+// (conv_stem_stats).  Its weight gradient (conv_stem_wrw) follows, with its
+// own description.  Geometry: conv_stem_plan.h.
 //
 //   B   the whole weight, padded from [64][7][21] to [64][7][24] + 8, stays in
 //       registers for the workgroup's whole walk: lane (c, h) holds for the
@@ -287,7 +288,332 @@ __global__ __launch_bounds__(kT, 2) void conv_stem_stats(
   }
 }
 
+// ---- weight gradient ----------------------------------------------------------
+//
+// dW[64][147] = dY^T[64][R] * Xcol[R][147], contracted over the R output pixels
+// (plan and layout of the planes: conv_stem_plan.h).
+//
+//   A   dY^T.  The band's pixels, contiguous in memory, are copied into a
+//       wrw_cell<64> image and read transposed by wrw_operand<64>, as in
+//       conv1x1_wrw and conv3x3_wrw.  A 16-deep step is 16 consecutive
+//       pixels: group 2s in lane half 0, group 2s + 1 in half 1
+//   B   lane (c, h) of column tile jk is column 32jk + c = 21r + 6a + q, and
+//       its eight K values are eight consecutive bf16 of plane q, from element
+//       ow0 + a + off(q) of strip row 2*ohl + r.  That run is only 2-byte
+//       aligned where a + off(q) is odd, so the lane reads the five aligned
+//       dwords around it and funnel-shifts them (four v_alignbit, by 0 or 16).
+//       Per lane and tile the address is a constant plus the group's
+//       2*ohl*row_bytes + 2*ow0: nothing but the group is worked out per step
+//   C   every wave holds all ten 32 x 32 tiles, 160 registers, and the four
+//       waves take the band's steps in turn: 2 A and 5 B operands feed ten
+//       MFMAs.  At the end of the walk waves 1 .. 3 hand their tiles to wave
+//       0 through LDS, which adds them in that order and stores the partial
+//
+// Staging.  A thread's unit of x is three 16-byte vectors, 24 elements, which
+// are exactly four elements of each of the six planes: six 8-byte LDS writes.
+// The first and last unit of every plane, and every unit of a strip row above
+// or below the image, are written as zeros on every band; a read reaches at
+// most element OW + 7 of a plane, the last of the last unit.  The next band
+// waits in registers during the MFMAs of this one and goes to the other
+// buffer after them: one barrier a band.
+//
+// Zeros.  The 13 pad columns and the half step past a band's last group are
+// cleared by a select, the half step on both operands; what the cleared lanes
+// read (the last real column's operand, the last group's, and for A whatever
+// follows the pixels in the buffer) lies inside the buffer.  No data is ever
+// multiplied by a zero that is not itself part of the convolution's padding.
+//
+// Every accumulator is one chain over the wave's steps in ascending order,
+// the waves and the splits are added in a fixed order: the same bits each run.
+
+struct StemWrwStage {
+  u32x4 dyv[kConvStemWrwDyVecs];
+  u32x4 xv[kConvStemWrwXUnits][3];
+
+  __device__ __forceinline__ void load(const uint4* __restrict__ dy,
+                                       const uint4* __restrict__ x,
+                                       const ConvStemWrwPlan& p, int band,
+                                       int tid) {
+    const ConvStemBand b = conv_stem_wrw_band(p, band);
+    const int vecs = b.live * p.ow * (kConvStemN / 8);
+    const uint4* src = dy + (int64_t)(b.image * p.oh + b.oh0) * p.ow *
+                                (kConvStemN / 8);
+#pragma unroll
+    for (int i = 0; i < kConvStemWrwDyVecs; i++)
+      if (i < p.dyvecs) {  // uniform
+        const int idx = tid + i * kT;
+        const u32x4 t =
+            *reinterpret_cast<const u32x4*>(src + (idx < vecs ? idx : 0));
+        dyv[i] = idx < vecs ? t : u32x4{0, 0, 0, 0};
+      }
+    const int row_vecs = 3 * p.w / 8;
+#pragma unroll
+    for (int i = 0; i < kConvStemWrwXUnits; i++)
+      if (i < p.xunits) {  // uniform
+        // opaque, so that the source is worked out per band and not kept in
+        // registers across the MFMAs (as StemStage::load)
+        int idx = tid + i * kT;
+        asm volatile("" : "+v"(idx));
+        const int rr = conv_stem_div((unsigned)idx, p.magic_units);
+        const int uu = idx - rr * p.units;
+        const int ih = 2 * b.oh0 - 3 + rr;
+        const bool live = rr < p.in_rows && ih >= 0 && ih < p.h && uu >= 1 &&
+                          uu <= p.units - 2;
+        const uint4* s =
+            x + (live ? (int64_t)(b.image * p.h + ih) * row_vecs + 3 * (uu - 1)
+                      : 0);
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          const u32x4 t = *reinterpret_cast<const u32x4*>(s + k);
+          xv[i][k] = live ? t : u32x4{0, 0, 0, 0};
+        }
+      }
+  }
+
+  __device__ __forceinline__ void store(char* buf, const ConvStemWrwPlan& p,
+                                        int tid) const {
+#pragma unroll
+    for (int i = 0; i < kConvStemWrwDyVecs; i++) {
+      const int idx = tid + i * kT;
+      if (i < p.dyvecs && idx < p.groups * 64)
+        *reinterpret_cast<u32x4*>(buf + wrw_cell<64>(idx >> 3, (idx >> 2) & 1) +
+                                  16 * (idx & 3)) = dyv[i];
+    }
+    char* planes = buf + p.dy_bytes;
+#pragma unroll
+    for (int i = 0; i < kConvStemWrwXUnits; i++) {
+      const int idx = tid + i * kT;
+      if (i < p.xunits && idx < p.in_rows * p.units) {
+        const int rr = conv_stem_div((unsigned)idx, p.magic_units);
+        const int uu = idx - rr * p.units;
+        char* at = planes + rr * p.row_bytes + 8 * uu;
+        // element k of the unit is strip position 24(uu-1) + 9 + k: plane
+        // (k + 3) % 6, so plane q takes the elements (q + 3) % 6 + 6j
+        auto el = [&](int k) {
+          const unsigned d = xv[i][k >> 3][(k >> 1) & 3];
+          return k & 1 ? d >> 16 : d & 0xffffu;
+        };
+#pragma unroll
+        for (int q = 0; q < 6; q++) {
+          const int k = (q + 3) % 6;
+          typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+          *reinterpret_cast<u32x2*>(at + q * p.plane) =
+              u32x2{el(k) | el(k + 6) << 16, el(k + 12) | el(k + 18) << 16};
+        }
+      }
+    }
+  }
+};
+
+__device__ __forceinline__ u32x4 stem_wrw_keep(bool keep, u32x4 v) {
+  return keep ? v : u32x4{0, 0, 0, 0};
+}
+
+__global__ __launch_bounds__(kT) void conv_stem_wrw(
+    const uint4* __restrict__ dy, const uint4* __restrict__ x,
+    float* __restrict__ part, ConvStemWrwPlan p) {
+  extern __shared__ uint4 lds[];
+  constexpr int NT = kConvStemWrwCols / 32;  // column tiles
+  char* bufs = reinterpret_cast<char*>(lds);
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int c = lane & 31, h = lane >> 5;
+  const int split = blockIdx.x;
+
+  // A: as conv1x1_wrw, lane 4q+pp of a 16-lane group supplies pixel 8h+q
+  const int in_cell = 32 * ((lane >> 4) & 1) + 8 * (lane & 3);
+  int an[2];
+#pragma unroll
+  for (int j = 0; j < 2; j++)
+    an[j] = wrw_cell<64>(8 * h + ((lane >> 2) & 3), j) + in_cell;
+  // B: the lane's column of each tile; a pad column reads the last real one
+  int cb[NT], sh[NT];
+#pragma unroll
+  for (int jk = 0; jk < NT; jk++) {
+    const int col = 32 * jk + c;
+    const ConvStemWrwCol cc = conv_stem_wrw_col(
+        p, col < kConvStemWrwReal ? col : kConvStemWrwReal - 1);
+    cb[jk] = cc.byte, sh[jk] = cc.shift;
+  }
+  const bool real_last = 32 * (NT - 1) + c < kConvStemWrwReal;
+
+  f32x16 acc[2][NT];
+#pragma unroll
+  for (int jm = 0; jm < 2; jm++)
+#pragma unroll
+    for (int jk = 0; jk < NT; jk++)
+#pragma unroll
+      for (int e = 0; e < 16; e++) acc[jm][jk][e] = 0.f;
+
+  int band = conv_stem_wrw_first(p, split);  // < end: no split is empty
+  const int end = conv_stem_wrw_end(p, split);
+  int buf = 0;
+  StemWrwStage st;
+  st.load(dy, x, p, band, tid);
+  st.store(bufs, p, tid);
+
+  struct Ops {
+    u32x4 a[2], b[NT];
+  };
+  while (band < end) {
+    const bool more = band + 1 < end;
+    if (more) st.load(dy, x, p, band + 1, tid);
+    // buffer `buf` is written, and the other one, read a band ago, is free
+    __syncthreads();
+    char* img = bufs + buf * p.buf_bytes;
+    const char* planes = img + p.dy_bytes;
+    const int groups = conv_stem_wrw_band(p, band).live * p.gpr;
+    const int steps = (groups + 1) / 2;
+
+    auto read = [&](Ops& o, int s) __attribute__((always_inline)) {
+      const int g = 2 * s + h;
+      const bool live = g < groups;
+      const int gc = live ? g : groups - 1;
+      const int ohl = p.gpr > 1 ? conv_stem_div((unsigned)gc, p.magic_gpr) : gc;
+      const char* xb =
+          planes + 2 * ohl * p.row_bytes + 16 * (gc - ohl * p.gpr);
+#pragma unroll
+      for (int j = 0; j < 2; j++)
+        o.a[j] = stem_wrw_keep(
+            live, __builtin_bit_cast(u32x4, wrw_operand<64>(img, an[j], s)));
+#pragma unroll
+      for (int jk = 0; jk < NT; jk++) {
+        const unsigned* d = reinterpret_cast<const unsigned*>(xb + cb[jk]);
+        const unsigned d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3], d4 = d[4];
+        const u32x4 t = {__builtin_amdgcn_alignbit(d1, d0, sh[jk]),
+                         __builtin_amdgcn_alignbit(d2, d1, sh[jk]),
+                         __builtin_amdgcn_alignbit(d3, d2, sh[jk]),
+                         __builtin_amdgcn_alignbit(d4, d3, sh[jk])};
+        o.b[jk] = stem_wrw_keep(live && (jk < NT - 1 || real_last), t);
+      }
+    };
+    auto mma = [&](const Ops& o) __attribute__((always_inline)) {
+#pragma unroll
+      for (int jk = 0; jk < NT; jk++)
+#pragma unroll
+        for (int jm = 0; jm < 2; jm++)
+          acc[jm][jk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              __builtin_bit_cast(bf16x8, o.a[jm]),
+              __builtin_bit_cast(bf16x8, o.b[jk]), acc[jm][jk], 0, 0, 0);
+    };
+    // two sets of operands: a step's reads are issued before the MFMAs of
+    // the wave's step before it
+    Ops o0, o1;
+    int s = wave;
+    if (s < steps) read(o0, s);
+    for (; s + 4 < steps; s += 8) {
+      read(o1, s + 4);
+      mma(o0);
+      if (s + 8 < steps) read(o0, s + 8);
+      mma(o1);
+    }
+    if (s < steps) mma(o0);
+    // nothing that waits for the loads above may move up among the MFMAs
+    __builtin_amdgcn_sched_barrier(0);
+    buf ^= 1;
+    if (more) st.store(bufs + buf * p.buf_bytes, p, tid);
+    band++;
+  }
+
+  // waves 1 .. 3 -> wave 0, register i of lane l at [wave-1][i][l]
+  __syncthreads();
+  float* sum = reinterpret_cast<float*>(lds);
+  constexpr int kRegs = 2 * NT * 16;
+  if (wave > 0) {
+#pragma unroll
+    for (int jm = 0; jm < 2; jm++)
+#pragma unroll
+      for (int jk = 0; jk < NT; jk++)
+#pragma unroll
+        for (int e = 0; e < 16; e++)
+          sum[((wave - 1) * kRegs + (jm * NT + jk) * 16 + e) * 64 + lane] =
+              acc[jm][jk][e];
+  }
+  __syncthreads();
+  if (wave == 0) {
+    float* out = part + (int64_t)split * kConvStemN * kConvStemWrwCols;
+#pragma unroll
+    for (int jm = 0; jm < 2; jm++)
+#pragma unroll
+      for (int jk = 0; jk < NT; jk++)
+#pragma unroll
+        for (int e = 0; e < 16; e++) {
+          float v = acc[jm][jk][e];
+#pragma unroll
+          for (int w = 0; w < 3; w++)
+            v += sum[(w * kRegs + (jm * NT + jk) * 16 + e) * 64 + lane];
+          out[(32 * jm + acc_row(e, h)) * kConvStemWrwCols + 32 * jk + c] = v;
+        }
+  }
+}
+
+// dw[64][147] = bf16(part[0] + part[1] + ...) without the pad columns, by the
+// lane groups of conv1x1_wrw_finalize: a vector of eight outputs is summed by
+// 16 lanes, lane j of them adding the splits j*per .. (j+1)*per - 1 in index
+// order, then the 16 sums as a tree over the lanes.  A wave takes four
+// vectors; the waves past the last vector repeat it and store nothing.
+__global__ __launch_bounds__(kT) void conv_stem_wrw_finalize(
+    const float* __restrict__ part, uint4* __restrict__ dw, int splits) {
+  constexpr int G = 16, VW = 64 / G;
+  constexpr int kVecs = kConvStemN * kConvStemWrwReal / 8;
+  static_assert(kConvStemN * kConvStemWrwReal % 8 == 0);
+  const int lane = threadIdx.x & 63;
+  const int wave = (blockIdx.x * kT + threadIdx.x) >> 6;
+  const int v = wave * VW + lane % VW;
+  const int vc = v < kVecs ? v : kVecs - 1;
+  const int j = lane / VW, per = (splits + G - 1) / G;
+  const int s1 = (j + 1) * per < splits ? (j + 1) * per : splits;
+  int at[8];
+#pragma unroll
+  for (int e = 0; e < 8; e++) {
+    const int o = 8 * vc + e, n = o / kConvStemWrwReal;
+    at[e] = n * kConvStemWrwCols + o - n * kConvStemWrwReal;
+  }
+  float f[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int s = j * per; s < s1; s++) {
+    const float* src = part + (int64_t)s * kConvStemN * kConvStemWrwCols;
+#pragma unroll
+    for (int e = 0; e < 8; e++) f[e] += src[at[e]];
+  }
+  for (int off = 32; off >= VW; off >>= 1)
+#pragma unroll
+    for (int e = 0; e < 8; e++) f[e] += __shfl_down(f[e], off);
+  if (j == 0 && v < kVecs)
+    dw[v] = make_uint4(fwd_pack_bf16(f[0], f[1]), fwd_pack_bf16(f[2], f[3]),
+                       fwd_pack_bf16(f[4], f[5]), fwd_pack_bf16(f[6], f[7]));
+}
+
 }  // namespace
+
+void launch_conv_stem_wrw(const ConvStemWrwPlan& p, const void* dy,
+                          const void* x, float* part, void* dw,
+                          hipStream_t stream) {
+  TORCH_CHECK(p.eligible, "conv_stem_wrw: shape is not eligible");
+  TORCH_CHECK(
+      p.dyvecs <= kConvStemWrwDyVecs && p.xunits <= kConvStemWrwXUnits &&
+          p.units == p.ow / 4 + 2 && p.plane == 8 * p.units &&
+          p.row_bytes == 6 * p.plane && p.in_rows == 2 * p.band_rows + 5 &&
+          p.gpr * 8 == p.ow && p.groups == p.band_rows * p.gpr &&
+          p.dy_bytes == (p.groups + 1) / 2 * 16 * kConvStemN * 2 &&
+          p.buf_bytes == p.dy_bytes + p.in_rows * p.row_bytes &&
+          p.grid == p.splits &&
+          (int64_t)(p.splits - 1) * p.bands_per_split < p.bands &&
+          (int64_t)p.splits * p.bands_per_split >= p.bands &&
+          p.lds_bytes >= 2 * p.buf_bytes &&
+          p.lds_bytes >= kConvStemWrwSumBytes && p.lds_bytes <= kConvLdsBytes,
+      "conv_stem_wrw: plan and kernel disagree");
+  static const hipError_t attr = hipFuncSetAttribute(
+      reinterpret_cast<const void*>(&conv_stem_wrw),
+      hipFuncAttributeMaxDynamicSharedMemorySize, kConvLdsBytes);
+  CGX_HIP_CHECK(attr);
+  hipLaunchKernelGGL(conv_stem_wrw, dim3(p.grid), dim3(kT), p.lds_bytes, stream,
+                     static_cast<const uint4*>(dy),
+                     static_cast<const uint4*>(x), part, p);
+  CGX_HIP_CHECK(hipGetLastError());
+  constexpr int kWaves = (kConvStemN * kConvStemWrwReal / 8 + 3) / 4;
+  hipLaunchKernelGGL(conv_stem_wrw_finalize, dim3((kWaves + 3) / 4), dim3(kT),
+                     0, stream, part, static_cast<uint4*>(dw), p.splits);
+  CGX_HIP_CHECK(hipGetLastError());
+}
 
 void launch_conv_stem_stats(const ConvStemPlan& p, const void* x, const void* w,
                             void* y, float* part, hipStream_t stream) {

@@ -142,4 +142,108 @@ __host__ __device__ inline unsigned conv_stem_keep(int group, int dword) {
 void launch_conv_stem_stats(const ConvStemPlan& p, const void* x, const void* w,
                             void* y, float* part, hipStream_t stream);
 
+// ---- weight gradient ----------------------------------------------------------
+//
+// dW[n][r][e] = sum over output pixels of dY[b, oh, ow, n] * X[b, 2oh+r-3][6ow-9+e]
+// (conv_stem_wrw in conv_stem_kernels.hip), e = 3s + c the 21 elements that a
+// filter row takes from an input row.  A GEMM with the output pixels as the
+// contracted index: M the 64 channels of dY, N the 147 columns 21r + e, padded
+// to 160.  A 16-deep MFMA step is two groups of eight consecutive ow of one
+// output row, one per lane half; W % 16 == 0, so no group crosses a row.
+//
+// A band is `band_rows` output rows of one image (the last of an image may be
+// short).  Its LDS buffer holds the band's pixels of dY as a wrw_cell<64> image
+// and its 2*band_rows + 5 input rows de-interleaved: with the forward's nine
+// zero elements on the left, strip position t = 6m + q goes to plane q, index
+// m, so that the eight pixels of a group, six elements apart in the row, are
+// eight consecutive bf16 of a plane.  A plane is stored from element -off(q),
+// off = 2 for q < 3 and 3 for q >= 3: then the 24 elements of three input
+// vectors fill exactly the four elements 4u .. 4u+3 of every plane (unit u),
+// the first and the last unit of a plane are zeros, and the operand of column
+// (r, e = 6a + q) for the group at (ohl, ow0) starts at element ow0 + a + off(q)
+// of plane q of strip row 2*ohl + r.
+//
+// The grid is persistent: workgroup s walks the bands s*bands_per_split ..
+// in order and writes one fp32 partial [64][160]; conv_stem_wrw_finalize adds
+// the partials in a fixed order and rounds once.
+constexpr int kConvStemWrwCols = 160;  // 147 columns, five 32-column tiles
+constexpr int kConvStemWrwReal = 147;
+// a thread's share of a band in registers: 16-byte vectors of dY, and units of
+// three vectors of x
+constexpr int kConvStemWrwDyVecs = 16, kConvStemWrwXUnits = 3;
+// The widest W % 16 == 0 at which two buffers of a one-row band fit in LDS:
+// 128 bytes of dY a pixel, OW rounded up to 16, and 7 rows of 6 planes of
+// W + 16 bytes, 2 * 81408 bytes at 752.  Its share per thread fits as well.
+constexpr int kConvStemWrwMaxW = 752;
+// three waves' accumulator tiles, for the sum at the end of the walk
+constexpr int kConvStemWrwSumBytes = 3 * kConvStemN * kConvStemWrwCols * 4;
+
+struct ConvStemWrwPlan {
+  int batch = 0, h = 0, w = 0;
+  bool eligible = false;
+  bool native = false;  // measured faster than the stock weight gradient
+  int oh = 0, ow = 0;
+  int band_rows = 0, bands_per_image = 0, bands = 0;
+  int in_rows = 0;     // strip rows: 2*band_rows + 5
+  int units = 0;       // 8-byte units of a plane: OW/4 + 2
+  int plane = 0;       // bytes of a plane
+  int row_bytes = 0;   // bytes of a strip row: 6 planes
+  int dy_bytes = 0;    // the dY image, a whole number of 16-pixel steps
+  int buf_bytes = 0;   // dy image + planes
+  int dyvecs = 0, xunits = 0;  // a thread's share of a full band
+  int gpr = 0;         // groups of an output row: OW/8
+  int groups = 0, steps = 0;            // of a full band
+  int last_groups = 0, last_steps = 0;  // of an image's last band
+  int splits = 0, grid = 0, bands_per_split = 0;
+  int lds_bytes = 0;
+  int64_t partial_floats = 0;  // splits * 64 * 160
+  unsigned magic_units = 0, magic_gpr = 0;  // conv_stem_div
+};
+
+// H even and >= 2, W a multiple of 16 up to kConvStemWrwMaxW,
+// 2 <= B*(H/2)*(W/2) <= kBnMaxRows.  `max_workgroups` > 0 caps the grid.
+ConvStemWrwPlan conv_stem_wrw_plan(int64_t batch, int64_t h, int64_t w,
+                                   int64_t max_workgroups = 0);
+
+// Band -> image, first output row, output rows (as conv_stem_band).
+__host__ __device__ inline ConvStemBand conv_stem_wrw_band(
+    const ConvStemWrwPlan& p, int band) {
+  const int image = band / p.bands_per_image;
+  const int oh0 = (band - image * p.bands_per_image) * p.band_rows;
+  const int left = p.oh - oh0;
+  return ConvStemBand{image, oh0, left < p.band_rows ? left : p.band_rows};
+}
+
+// The bands workgroup `split` walks: first .. end-1, never none.
+__host__ __device__ inline int conv_stem_wrw_first(const ConvStemWrwPlan& p,
+                                                   int split) {
+  return split * p.bands_per_split;
+}
+__host__ __device__ inline int conv_stem_wrw_end(const ConvStemWrwPlan& p,
+                                                 int split) {
+  const int end = (split + 1) * p.bands_per_split;
+  return end < p.bands ? end : p.bands;
+}
+
+// Column 21r + e of the GEMM -> where its operands start in the planes, apart
+// from the group's own 2*ohl*row_bytes + 2*ow0: `byte` is 4-byte aligned and
+// the operand starts `shift` bits into it.  Columns >= 147 have no operand.
+struct ConvStemWrwCol {
+  int byte, shift;
+};
+__host__ __device__ inline ConvStemWrwCol conv_stem_wrw_col(
+    const ConvStemWrwPlan& p, int col) {
+  const int r = col / 21, e = col - 21 * r;
+  const int a = e / 6, q = e - 6 * a;
+  const int at = a + (q < 3 ? 2 : 3);
+  return ConvStemWrwCol{r * p.row_bytes + q * p.plane + 2 * (at & ~1),
+                        16 * (at & 1)};
+}
+
+// dw[64, 7, 7, 3] bf16 from dy[B, H/2, W/2, 64] and x[B, H, W, 3] bf16, through
+// part[splits, 64, 160] fp32; every pointer 16-byte aligned.
+void launch_conv_stem_wrw(const ConvStemWrwPlan& p, const void* dy,
+                          const void* x, float* part, void* dw,
+                          hipStream_t stream);
+
 }  // namespace cgx

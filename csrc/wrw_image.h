@@ -1,5 +1,6 @@
 // The LDS image and the transposed operand read that the weight-gradient
-// kernels share (conv1x1_kernels.hip, conv3x3_kernels.hip).  Device code: only
+// kernels share (conv1x1_kernels.hip, conv3x3_kernels.hip,
+// conv_stem_kernels.hip).  Device code: only
 // .hip files include this.  The layout is argued at conv1x1_wrw.
 #pragma once
 

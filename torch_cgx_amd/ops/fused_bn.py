@@ -619,12 +619,15 @@ class _ConvStem(torch.autograd.Function):
     """``(y, part) = f(x, weight)``: ``conv2d(x, weight, stride=2,
     padding=3)``, by the native implicit GEMM with the BatchNorm partials of
     ``y`` (``_C.conv_stem_stats``) where ``native_fwd`` says so, else stock
-    with ``part`` None.  The backward is the stock one."""
+    with ``part`` None.  With ``native_wrw`` the weight gradient comes from
+    the native implicit GEMM (``_C.conv_stem_wrw``) where it takes the
+    gradient that arrives; the stock backward computes what remains."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
-    def forward(ctx, x, weight, native_fwd):
+    def forward(ctx, x, weight, native_fwd, native_wrw=False):
         ctx.save_for_backward(x, weight)
+        ctx.native_wrw = native_wrw
         if native_fwd:
             y, part = _C.conv_stem_stats(x, weight)
             ctx.mark_non_differentiable(part)
@@ -636,10 +639,26 @@ class _ConvStem(torch.autograd.Function):
     def backward(ctx, dy, _dpart):
         x, weight = ctx.saved_tensors
         need_dx, need_dw = ctx.needs_input_grad[:2]
-        dx, dw, _ = torch.ops.aten.convolution_backward(
-            dy, x, weight, None, (2, 2), (3, 3), (1, 1), False, (0, 0), 1,
-            (need_dx, need_dw, False))
-        return (dx if need_dx else None), (dw if need_dw else None), None
+        dx = dw = None
+        if need_dw and ctx.native_wrw and _C.conv_stem_wrw_eligible(dy, x):
+            dw, need_dw = _C.conv_stem_wrw(dy, x), False
+        if need_dx or need_dw:
+            dx_stock, dw_stock, _ = torch.ops.aten.convolution_backward(
+                dy, x, weight, None, (2, 2), (3, 3), (1, 1), False, (0, 0), 1,
+                (need_dx, need_dw, False))
+            dx = dx_stock if need_dx else dx
+            dw = dw_stock if need_dw else dw
+        return dx, dw, None, None
+
+
+def native_conv_stem_wrw_mode() -> str:
+    """``CGX_NATIVE_CONV_STEM_WRW``, the switch of the stem's weight gradient
+    (``_C.conv_stem_wrw``): "0" off, "all" every eligible problem, else ("1",
+    the default) the problems its plan has measured faster.  Off where
+    ``CGX_FUSED_BN`` is; ``CGX_NATIVE_CONV_STEM`` does not reach it."""
+    if not fused_bn_enabled():
+        return "0"
+    return os.environ.get("CGX_NATIVE_CONV_STEM_WRW", "1")
 
 
 def native_conv_stem_mode() -> str:
@@ -652,13 +671,9 @@ def native_conv_stem_mode() -> str:
     return os.environ.get("CGX_NATIVE_CONV_STEM", "1")
 
 
-def _conv_stem_native(conv, bn, x, pool) -> bool:
-    """Whether ``_C.conv_stem_stats`` is to compute ``conv(x)`` for ``bn``
-    and ``pool``: the switch and the plan say so and the modules and tensors
-    are what the kernels take."""
-    mode = native_conv_stem_mode()
-    if mode == "0":
-        return False
+def _conv_stem_takes(conv, x) -> bool:
+    """Whether ``conv`` is the stem and ``conv.weight`` and ``x`` are what
+    its native kernels take."""
     if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == (7, 7)
             and conv.stride == (2, 2) and conv.padding == (3, 3)
             and conv.dilation == (1, 1) and conv.groups == 1
@@ -678,8 +693,18 @@ def _conv_stem_native(conv, bn, x, pool) -> bool:
                 and (t.data_ptr() % 16 == 0 if t.dtype == torch.bfloat16
                      else autocast and t.dtype == torch.float32))
 
-    if not (takes(x) and takes(w) and w.device == x.device
-            and x.shape[1] == 3 and _pool_is_3x3_s2_p1(pool)):
+    return (takes(x) and takes(w) and w.device == x.device
+            and x.shape[1] == 3)
+
+
+def _conv_stem_native(conv, bn, x, pool) -> bool:
+    """Whether ``_C.conv_stem_stats`` is to compute ``conv(x)`` for ``bn``
+    and ``pool``: the switch and the plan say so and the modules and tensors
+    are what the kernels take."""
+    mode = native_conv_stem_mode()
+    if mode == "0":
+        return False
+    if not (_conv_stem_takes(conv, x) and _pool_is_3x3_s2_p1(pool)):
         return False
     plan = _C.conv_stem_plan(x.shape[0], x.shape[2], x.shape[3])
     # the plan's bounds on the output's pixels are the BatchNorm kernels'
@@ -687,13 +712,29 @@ def _conv_stem_native(conv, bn, x, pool) -> bool:
             and _bn_native(bn))
 
 
+def _conv_stem_wrw_native(conv, x) -> bool:
+    """Whether ``_C.conv_stem_wrw`` is to compute the gradient of
+    ``conv.weight``: the switch and the plan say so."""
+    mode = native_conv_stem_wrw_mode() if torch.is_grad_enabled() else "0"
+    if mode == "0" or not conv.weight.requires_grad:
+        return False
+    if not _conv_stem_takes(conv, x):
+        return False
+    plan = _C.conv_stem_wrw_plan(x.shape[0], x.shape[2], x.shape[3])
+    return plan["eligible"] and (plan["native"] or mode == "all")
+
+
 def conv_stem_bn_act_pool(conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d,
                           x: torch.Tensor, pool: torch.nn.Module
                           ) -> torch.Tensor:
     """``pool(relu(bn(conv(x))))`` for the stem: where the native forward
     runs (``native_conv_stem_mode``), ``bn`` takes its statistics from the
-    partials that come with the output."""
-    if not _conv_stem_native(conv, bn, x, pool):
+    partials that come with the output; where the native weight gradient
+    runs (``native_conv_stem_wrw_mode``), the backward takes it.  Each has
+    its own switch and its plan's table, as in ``_conv3x3``."""
+    fwd = _conv_stem_native(conv, bn, x, pool)
+    wrw = _conv_stem_wrw_native(conv, x)
+    if not (fwd or wrw):
         return bn_act_pool(bn, conv(x), pool)
-    y, part = _ConvStem.apply(x, conv.weight, True)
+    y, part = _ConvStem.apply(x, conv.weight, fwd, wrw)
     return bn_act_pool(bn, y, pool, part=part)
