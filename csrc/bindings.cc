@@ -1558,6 +1558,79 @@ py::dict py_conv3x3_fwd_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
       conv3x3_fwd_plan(batch, h, w, c, n, max_workgroups));
 }
 
+// ---- 3x3 / stride 2 convolution forward with statistics ------------------------
+
+Conv3x3S2FwdPlan conv3x3s2_fwd_plan_of(const at::Tensor& x, const at::Tensor& w,
+                                       int64_t max_workgroups = 0) {
+  return conv3x3s2_fwd_plan(x.size(0), x.size(2), x.size(3), x.size(1),
+                            w.size(0), max_workgroups);
+}
+
+// the tensors of py_conv3x3_fwd_eligible, with even H and W
+bool py_conv3x3s2_fwd_eligible(const at::Tensor& x, const at::Tensor& w) {
+  return bn_tensor_ok(x) && w.is_cuda() && w.device() == x.device() &&
+         w.scalar_type() == at::kBFloat16 && w.dim() == 4 && w.size(2) == 3 &&
+         w.size(3) == 3 && w.size(1) == x.size(1) &&
+         w.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+         reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0 &&
+         conv3x3s2_fwd_plan_of(x, w).eligible;
+}
+
+// conv2d(x, weight, stride=2, padding=1) -> (y, part), as py_conv3x3_stats
+std::tuple<at::Tensor, at::Tensor> py_conv3x3s2_stats(const at::Tensor& x,
+                                                      const at::Tensor& weight,
+                                                      int64_t max_workgroups) {
+  TORCH_CHECK(max_workgroups >= 0, "conv3x3s2_stats: max_workgroups >= 0");
+  TORCH_CHECK(py_conv3x3s2_fwd_eligible(x, weight),
+              "conv3x3s2_stats: input or weight is not eligible");
+  const Conv3x3S2FwdPlan p = conv3x3s2_fwd_plan_of(x, weight, max_workgroups);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device().index());
+  auto y = at::empty({x.size(0), p.n, p.ho, p.wo}, x.options(),
+                     at::MemoryFormat::ChannelsLast);
+  auto part = at::empty({p.splits, p.pstride}, x.options().dtype(at::kFloat));
+  launch_conv3x3s2_stats(p, x.data_ptr(), weight.data_ptr(), y.data_ptr(),
+                         part.data_ptr<float>(), bn_stream(x));
+  return {y, part};
+}
+
+py::dict py_conv3x3s2_fwd_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
+                               int64_t n, int64_t max_workgroups) {
+  const Conv3x3S2FwdPlan p =
+      conv3x3s2_fwd_plan(batch, h, w, c, n, max_workgroups);
+  py::dict d = conv3x3_fwd_plan_dict(p);
+  d["ho"] = p.ho;
+  d["wo"] = p.wo;
+  d["plane_base"] = std::vector<int>(p.plane_base, p.plane_base + 4);
+  d["plane_rows"] = std::vector<int>(p.plane_rows, p.plane_rows + 4);
+  return d;
+}
+
+// Test seam: entry [row, tap] is the input pixel (b*H + ih)*W + iw whose
+// channels the kernel multiplies with tap 3r + s of the weight for output
+// pixel `row`, read through the planes of the row's tile, or -1 where it
+// clears the operand.
+at::Tensor py_conv3x3s2_fwd_taps(int64_t batch, int64_t h, int64_t w, int64_t c,
+                                 int64_t n) {
+  const Conv3x3S2FwdPlan p = conv3x3s2_fwd_plan(batch, h, w, c, n);
+  TORCH_CHECK(p.eligible, "conv3x3s2_fwd_taps: shape is not eligible");
+  auto out = at::empty({p.rows, 9}, at::TensorOptions().dtype(at::kLong));
+  int64_t* o = out.data_ptr<int64_t>();
+  for (int row = 0; row < p.rows; row++) {
+    const unsigned valid = conv3x3s2_fwd_taps(p, row);
+    const int t = row / p.tile_rows, m = row % p.tile_rows;
+    for (int tap = 0; tap < 9; tap++) {
+      const int pl = 2 * (tap / 3 != 1) + (tap % 3 != 1);
+      const int e = conv3x3s2_fwd_strip_index(p, m, tap);
+      TORCH_CHECK(e >= p.plane_base[pl] &&
+                      e < p.plane_base[pl] + p.plane_rows[pl],
+                  "conv3x3s2_fwd_taps: off the plane");
+      o[row * 9 + tap] =
+          (valid >> tap) & 1 ? conv3x3s2_fwd_strip_pixel(p, t, e) : -1;
+    }
+  }
+  return out;
+}
+
 // ---- stem convolution forward with statistics ---------------------------------
 
 // x as the BatchNorm kernels take it, with three channels, and a dense,
@@ -1808,9 +1881,7 @@ py::dict py_conv3x3_bwd_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
 // Test seam: the kernel's walk replayed on the host.  Entry [wg, i] holds
 // (n0, split, row0, row1) of the i-th tile of workgroup wg, -1 once it has
 // run out of tiles.
-at::Tensor py_conv3x3_fwd_walk(int64_t batch, int64_t h, int64_t w, int64_t c,
-                               int64_t n, int64_t max_workgroups) {
-  const Conv3x3FwdPlan p = conv3x3_fwd_plan(batch, h, w, c, n, max_workgroups);
+at::Tensor conv3x3_fwd_walk_of(const Conv3x3FwdPlan& p) {
   TORCH_CHECK(p.eligible, "conv3x3_fwd_walk: shape is not eligible");
   auto out = at::full({p.grid, p.tiles_per_split, 4}, -1,
                       at::TensorOptions().dtype(at::kLong));
@@ -1828,6 +1899,17 @@ at::Tensor py_conv3x3_fwd_walk(int64_t batch, int64_t h, int64_t w, int64_t c,
     }
   }
   return out;
+}
+at::Tensor py_conv3x3_fwd_walk(int64_t batch, int64_t h, int64_t w, int64_t c,
+                               int64_t n, int64_t max_workgroups) {
+  return conv3x3_fwd_walk_of(
+      conv3x3_fwd_plan(batch, h, w, c, n, max_workgroups));
+}
+at::Tensor py_conv3x3s2_fwd_walk(int64_t batch, int64_t h, int64_t w,
+                                 int64_t c, int64_t n,
+                                 int64_t max_workgroups) {
+  return conv3x3_fwd_walk_of(
+      conv3x3s2_fwd_plan(batch, h, w, c, n, max_workgroups));
 }
 
 // Test seam: entry [row, tap] is the pixel whose channels the kernel
@@ -2366,6 +2448,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("h"), py::arg("w"), py::arg("c"), py::arg("n"),
         "Test seam: [rows, 9] int64, the pixel each tap of each output pixel "
         "reads through its tile's strip, -1 where the operand is cleared.");
+  m.def("conv3x3s2_stats", &cgx::py_conv3x3s2_stats, py::arg("x"),
+        py::arg("weight"), py::arg("max_workgroups") = 0,
+        "conv2d(x, weight, stride=2, padding=1) of a 3x3 convolution of an "
+        "image with even sides by the native implicit GEMM -> (y, part), as "
+        "conv3x3_stats.  max_workgroups > 0 caps the grid.");
+  m.def("conv3x3s2_fwd_eligible", &cgx::py_conv3x3s2_fwd_eligible,
+        py::arg("x"), py::arg("weight"),
+        "True where conv3x3s2_stats takes (x, weight): as "
+        "conv3x3_fwd_eligible, with H and W even, W <= 62 and H <= 2048.");
+  m.def("conv3x3s2_fwd_plan", &cgx::py_conv3x3s2_fwd_plan, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("c"), py::arg("n"),
+        py::arg("max_workgroups") = 0,
+        "The launch geometry of conv3x3s2_stats for an input [batch, c, h, "
+        "w]: the keys of conv3x3_fwd_plan (rows are output pixels), the "
+        "output size and the four parity planes of the strip.");
+  m.def("conv3x3s2_fwd_walk", &cgx::py_conv3x3s2_fwd_walk, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("c"), py::arg("n"),
+        py::arg("max_workgroups") = 0,
+        "Test seam: conv3x3_fwd_walk for conv3x3s2_stats.");
+  m.def("conv3x3s2_fwd_taps", &cgx::py_conv3x3s2_fwd_taps, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("c"), py::arg("n"),
+        "Test seam: [rows, 9] int64, the input pixel each tap of each output "
+        "pixel reads through its tile's planes, -1 where the operand is "
+        "cleared.");
   m.def("conv_stem_stats", &cgx::py_conv_stem_stats, py::arg("x"),
         py::arg("weight"), py::arg("max_workgroups") = 0,
         "conv2d(x, weight, stride=2, padding=3) of the 3 -> 64 channel 7x7 "

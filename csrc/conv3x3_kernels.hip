@@ -1,8 +1,9 @@
 // The 3x3 / stride 1 / padding 1 convolution on channels_last bf16 tensors as
 // implicit GEMMs: the weight gradient (conv3x3_wrw, first), the forward that
 // also produces BatchNorm partials (conv3x3_stats, below it) and the input
-// gradient (conv3x3_bwd_data, last), each with its own description.
-// Geometry: conv3x3_plan.h.
+// gradient (conv3x3_bwd_data, last), each with its own description; between
+// the last two the forward of the 3x3 / stride 2 / padding 1 convolution
+// (conv3x3s2_stats).  Geometry: conv3x3_plan.h.
 //
 // dW[n][(3r+s)*C + c] = sum over pixels of dY[b, h, w, n] * X[b, h+r-1, w+s-1, c].
 // Both operands have the contracted index slow, so both MFMA operands are
@@ -781,6 +782,250 @@ void launch_fwd3x3(const Conv3x3FwdPlan& p, const void* x, const void* w,
   CGX_HIP_CHECK(hipGetLastError());
 }
 
+// ---- stride-2 forward with BatchNorm partials ---------------------------------
+//
+// y = conv2d(x, w, stride 2, padding 1) of an image with even sides, and the
+// partials of y.  Geometry: Conv3x3S2FwdPlan.
+//
+//   A   the strip of a tile, four parity planes of one 32-channel chunk of X
+//       behind one another, 64 bytes an entry in the fwd_slot layout.  Entry
+//       e holds input pixel conv3x3s2_fwd_strip_pixel(e); a thread keeps the
+//       addresses of its (at most nine) vectors of a tile, which do not depend
+//       on the chunk, so the two divisions per vector are paid once a tile.
+//       Lane (c, h) of wave w reads for tap (r, s) the 16 bytes of entry
+//       conv3x3s2_fwd_strip_index(32*w + c, 3r + s): 16 consecutive entries
+//       of one plane per pass, conflict-free at every start like the stride-1
+//       strip, and clears them where conv3x3s2_fwd_taps has no bit
+//   B   the weight chunk of conv3x3_stats, streamed: [9][64][32]
+//   C   a wave owns 32 rows x 64 channels, two accumulator tiles: one read of
+//       A and two of B feed two MFMAs per 16-deep step and tap
+//
+// A stage is one chunk of one tile, 36 MFMAs a wave, staged through registers
+// behind the MFMAs of the stage before and ordered by one barrier, as in
+// conv3x3_stats.  The epilogue, the per-lane pivot and the tree of the eight
+// runs are conv3x3_stats' with one sub-tile per wave.
+
+static_assert(kConv3x3S2TileRows == 4 * 32);
+
+// The eight runs of every channel of a workgroup -> its partial row: the
+// tree at the end of conv3x3_stats, which keeps its own copy so that its
+// register allocation stays what RESULTS.md records.  `sc` is LDS that nobody
+// reads any more.
+__device__ __forceinline__ void fwd_merge_runs(float* sc, const Moments<2>& mo,
+                                               const float (&pivot)[2],
+                                               float* row, int n, int n0,
+                                               int ntile, int tid) {
+  constexpr int BN = kConv3x3FwdBn;
+  const int wave = tid >> 6, c = tid & 31, h = (tid & 63) >> 5;
+  __syncthreads();
+  const int run = wave * 2 + h;
+#pragma unroll
+  for (int j = 0; j < 2; j++) {
+    sc[run * BN + j * 32 + c] = mo.mean[j];
+    sc[(8 + run) * BN + j * 32 + c] = mo.m2[j];
+    sc[(16 + run) * BN + j * 32 + c] = pivot[j];
+  }
+  if (c == 0) sc[24 * BN + run] = mo.n;
+  __syncthreads();
+  if (tid < BN) {
+    Moments<1> m[8];
+    float pv[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+      m[r].n = sc[24 * BN + r];
+      m[r].mean[0] = sc[r * BN + tid];
+      m[r].m2[0] = sc[(8 + r) * BN + tid];
+      pv[r] = sc[(16 + r) * BN + tid];
+    }
+#pragma unroll
+    for (int step = 1; step < 8; step *= 2)
+#pragma unroll
+      for (int r = 0; r < 8; r += 2 * step) {
+        pv[r] = m[r].n > 0.f ? pv[r] : pv[r + step];
+        const float mb[1] = {m[r + step].n > 0.f
+                                 ? (pv[r + step] - pv[r]) + m[r + step].mean[0]
+                                 : 0.f};
+        m[r].merge(m[r + step].n, mb, m[r + step].m2);
+      }
+    row[n0 + tid] = pv[0] + m[0].mean[0];
+    row[n + n0 + tid] = m[0].m2[0];
+    if (tid == 0) row[2 * n + ntile] = m[0].n;
+  }
+}
+
+struct S2Stage {
+  u32x4 wv[kFwdWShare], xv[kConv3x3S2XVecs];
+  int src[kConv3x3S2XVecs];  // the thread's vectors of chunk 0 of the tile
+  __device__ __forceinline__ void aim(const Conv3x3S2FwdPlan& p, int tile,
+                                      int tid) {
+#pragma unroll
+    for (int i = 0; i < kConv3x3S2XVecs; i++)
+      if (i < p.xvecs) {  // uniform
+        const int idx = tid + i * kT;
+        src[i] = conv3x3s2_fwd_strip_pixel(p, tile, idx >> 2) * (p.c / 8) +
+                 (idx & 3);
+      }
+  }
+  __device__ __forceinline__ void load(const uint4* __restrict__ x,
+                                       const uint4* __restrict__ w,
+                                       const Conv3x3S2FwdPlan& p, int n0,
+                                       int kc, int tid) {
+#pragma unroll
+    for (int i = 0; i < kFwdWShare; i++)
+      wv[i] = *reinterpret_cast<const u32x4*>(
+          fwd_w_src(w, p, n0, kc, tid + i * kT));
+#pragma unroll
+    for (int i = 0; i < kConv3x3S2XVecs; i++)
+      if (i < p.xvecs)
+        xv[i] = *reinterpret_cast<const u32x4*>(
+            x + src[i] + kc * (kConv3x3FwdKc / 8));
+  }
+  __device__ __forceinline__ void store(uint4* wb, uint4* xb,
+                                        const Conv3x3S2FwdPlan& p,
+                                        int tid) const {
+#pragma unroll
+    for (int i = 0; i < kFwdWShare; i++) {
+      const int idx = tid + i * kT;
+      *reinterpret_cast<u32x4*>(wb + fwd_slot(idx >> 2, idx & 3)) = wv[i];
+    }
+#pragma unroll
+    for (int i = 0; i < kConv3x3S2XVecs; i++)
+      if (i < p.xvecs) {
+        const int idx = tid + i * kT;
+        *reinterpret_cast<u32x4*>(xb + fwd_slot(idx >> 2, idx & 3)) = xv[i];
+      }
+  }
+};
+
+__global__ __launch_bounds__(kT) void conv3x3s2_stats(
+    const uint4* __restrict__ x, const uint4* __restrict__ w,
+    uint4* __restrict__ y, float* __restrict__ part, Conv3x3S2FwdPlan p) {
+  extern __shared__ uint4 lds[];
+  constexpr int BN = kConv3x3FwdBn, M = kConv3x3S2TileRows;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int c = lane & 31, h = lane >> 5;
+  const int ntile = conv3x3_fwd_ntile(p, blockIdx.x);
+  const int split = conv3x3_fwd_split(p, blockIdx.x);
+  const int n0 = ntile * BN, nvec = p.n / 8;
+  const int xbuf = p.xvecs * kT;  // vectors of a strip buffer
+  uint4* wimg = lds;              // two weight chunks
+  uint4* ximg = lds + 2 * kFwdWVecs;  // two strips
+  uint4* stage = ximg + 2 * xbuf + wave * 256;  // [32 rows][64 channels]
+
+  S2Stage st;
+  int tile = split, kc = 0, buf = 0;  // split < row_tiles
+  st.aim(p, tile, tid);
+  st.load(x, w, p, n0, 0, tid);
+  st.store(wimg, ximg, p, tid);
+
+  // the entry of each tap for the lane's row, the same on every tile
+  int at[9];
+#pragma unroll
+  for (int tap = 0; tap < 9; tap++)
+    at[tap] = conv3x3s2_fwd_strip_index(p, wave * 32 + c, tap);
+
+  Moments<2> mo;  // of v - pivot, as in conv3x3_stats
+  float pivot[2] = {0.f, 0.f};
+  auto push = [&](const float (&v)[2]) __attribute__((always_inline)) {
+    float d[2];
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+      pivot[j] = mo.n == 0.f ? v[j] : pivot[j];
+      d[j] = v[j] - pivot[j];
+    }
+    mo.push(d);
+  };
+  f32x16 acc[2];
+#pragma unroll
+  for (int j = 0; j < 2; j++)
+#pragma unroll
+    for (int e = 0; e < 16; e++) acc[j][e] = 0.f;
+  unsigned valid = 0;
+
+  while (tile < p.row_tiles) {
+    int nkc = kc + 1, ntl = tile;
+    if (nkc == p.nchunks) nkc = 0, ntl = tile + p.splits;
+    const bool more = ntl < p.row_tiles;
+    if (more) {
+      if (nkc == 0) st.aim(p, ntl, tid);
+      st.load(x, w, p, n0, nkc, tid);
+    }
+    // buffer `buf` is written, and the other one, read a stage ago, is free
+    __syncthreads();
+    if (kc == 0) valid = conv3x3s2_fwd_taps(p, tile * M + wave * 32 + c);
+    const uint4* wl = wimg + buf * kFwdWVecs;
+    const uint4* xl = ximg + buf * xbuf;
+    uint4 av[2], bv[2][2];  // the operands of this step and the next
+    auto read = [&](int u) {
+      const int tap = u >> 1, q = 2 * (u & 1) + h;
+      const uint4 v = xl[fwd_slot(at[tap], q)];
+      const unsigned m = 0u - ((valid >> tap) & 1u);
+      av[u & 1] = make_uint4(v.x & m, v.y & m, v.z & m, v.w & m);
+#pragma unroll
+      for (int j = 0; j < 2; j++)
+        bv[u & 1][j] = wl[fwd_slot(tap * 64 + j * 32 + c, q)];
+    };
+    read(0);
+#pragma unroll
+    for (int u = 0; u < 18; u++) {
+      if (u + 1 < 18) read(u + 1);
+#pragma unroll
+      for (int j = 0; j < 2; j++)
+        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            __builtin_bit_cast(bf16x8, av[u & 1]),
+            __builtin_bit_cast(bf16x8, bv[u & 1][j]), acc[j], 0, 0, 0);
+    }
+    // nothing that waits for the loads above may move up among the MFMAs
+    __builtin_amdgcn_sched_barrier(0);
+    buf ^= 1;
+    if (more) st.store(wimg + buf * kFwdWVecs, ximg + buf * xbuf, p, tid);
+
+    if (nkc == 0) {  // the tile is complete: round, push, store
+      const int r0 = tile * M + wave * 32;
+      const int live = p.rows - r0 < 32 ? p.rows - r0 : 32;  // may be <= 0
+      unsigned pk[2][8];
+#pragma unroll
+      for (int j = 0; j < 2; j++)
+#pragma unroll
+        for (int e = 0; e < 8; e++)
+          pk[j][e] = fwd_pack_bf16(acc[j][2 * e], acc[j][2 * e + 1]);
+#pragma unroll
+      for (int e = 0; e < 8; e++) {
+        float lo[2], hi[2];
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+          lo[j] = __uint_as_float(pk[j][e] << 16);
+          hi[j] = __uint_as_float(pk[j][e] & 0xffff0000u);
+        }
+        if (acc_row(2 * e, h) < live) push(lo);
+        if (acc_row(2 * e + 1, h) < live) push(hi);
+      }
+      fwd_store_subtile(pk, stage, y, r0, live, nvec, n0, lane);
+#pragma unroll
+      for (int j = 0; j < 2; j++)
+#pragma unroll
+        for (int e = 0; e < 16; e++) acc[j][e] = 0.f;
+    }
+    kc = nkc, tile = ntl;
+  }
+
+  fwd_merge_runs(reinterpret_cast<float*>(lds), mo, pivot,
+                 part + (int64_t)split * p.pstride, p.n, n0, ntile, tid);
+}
+
+void launch_fwd3x3s2(const Conv3x3S2FwdPlan& p, const void* x, const void* w,
+                     void* y, float* part, hipStream_t stream) {
+  static const hipError_t attr = hipFuncSetAttribute(
+      reinterpret_cast<const void*>(&conv3x3s2_stats),
+      hipFuncAttributeMaxDynamicSharedMemorySize, kConvLdsBytes);
+  CGX_HIP_CHECK(attr);
+  hipLaunchKernelGGL(conv3x3s2_stats, dim3(p.grid), dim3(kT), p.lds_bytes,
+                     stream, static_cast<const uint4*>(x),
+                     static_cast<const uint4*>(w), static_cast<uint4*>(y),
+                     part, p);
+  CGX_HIP_CHECK(hipGetLastError());
+}
+
 // ---- input gradient -----------------------------------------------------------
 //
 // dX[b, c, h, w] = sum over n, r, s of dY[b, n, h+1-r, w+1-s] * W[n, c, r, s]:
@@ -968,6 +1213,19 @@ void launch_conv3x3_stats(const Conv3x3FwdPlan& p, const void* x, const void* w,
               "conv3x3_stats: plan and kernel disagree");
   if (p.resident) launch_fwd3x3<true>(p, x, w, y, part, stream);
   else launch_fwd3x3<false>(p, x, w, y, part, stream);
+}
+
+void launch_conv3x3s2_stats(const Conv3x3S2FwdPlan& p, const void* x,
+                            const void* w, void* y, float* part,
+                            hipStream_t stream) {
+  TORCH_CHECK(p.eligible, "conv3x3s2_stats: shape is not eligible");
+  TORCH_CHECK(p.bn == kConv3x3FwdBn && p.kc == kConv3x3FwdKc &&
+                  p.tile_rows == kConv3x3S2TileRows &&
+                  p.xvecs <= kConv3x3S2XVecs && p.strip_rows <= 64 * p.xvecs &&
+                  p.plane_base[3] + p.plane_rows[3] == p.strip_rows &&
+                  p.splits <= p.row_tiles && p.lds_bytes <= kConvLdsBytes,
+              "conv3x3s2_stats: plan and kernel disagree");
+  launch_fwd3x3s2(p, x, w, y, part, stream);
 }
 
 void launch_conv3x3_wrw(const Conv3x3WrwPlan& p, const void* dy, const void* x,

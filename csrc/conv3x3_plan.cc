@@ -54,6 +54,16 @@ constexpr Measured3x3 kNativeBwd3x3[] = {
     {256, 7, 7, 512, 512},
 };
 
+// The same rule for conv3x3s2_stats followed by bn_act_forward with its
+// partials against MIOpen's stride-2 forward followed by bn_act_forward with
+// a statistics pass (benchmarks/conv3x3_s2_fwd_shapes.py); batch, H, W of the
+// input.  Of the three strided problems of ResNet-50 at batch 256 only the
+// deepest met it; 128->128 from 56x56 and 256->256 from 28x28 tie with the
+// stock pair and stay stock.
+constexpr Measured3x3 kNativeFwd3x3S2[] = {
+    {256, 14, 14, 512, 512},
+};
+
 bool pow2_in(int64_t v, int64_t lo, int64_t hi) {
   return v >= lo && v <= hi && (v & (v - 1)) == 0;
 }
@@ -265,6 +275,56 @@ Conv3x3FwdPlan conv3x3_fwd_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
   p.grid = p.ntiles * p.splits;
   p.tiles_per_split = (p.row_tiles + p.splits - 1) / p.splits;
   p.run = 32 * p.tiles_per_split;
+  p.lds_bytes = 2 * kConv3x3FwdWBytes + 2 * p.xvecs * 64 * p.kc * 2 +
+                kConvStageBytes;
+  p.pstride = 2 * p.n + p.ntiles;
+  p.partial_floats = (int64_t)p.splits * p.pstride;
+  return p;
+}
+
+Conv3x3S2FwdPlan conv3x3s2_fwd_plan(int64_t batch, int64_t h, int64_t w,
+                                    int64_t c, int64_t n,
+                                    int64_t max_workgroups) {
+  Conv3x3S2FwdPlan p;
+  p.bn = kConv3x3FwdBn;
+  p.tile_rows = kConv3x3S2TileRows;
+  p.kc = kConv3x3FwdKc;
+  const int64_t strip = 4 * p.tile_rows + w + 2;  // 2 * Wo of halo
+  p.eligible = pow2_in(c, 64, 512) && pow2_in(n, 64, 512) && batch >= 1 &&
+               h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0 && h <= 2048 &&
+               batch <= kBnMaxRows && batch * h * w <= kBnMaxRows &&
+               batch * h * w >= 8 && strip <= 64 * kConv3x3S2XVecs;
+  if (!p.eligible) return p;
+  p.batch = (int)batch, p.h = (int)h, p.w = (int)w, p.c = (int)c, p.n = (int)n;
+  p.ho = p.h / 2, p.wo = p.w / 2;
+  p.rows = p.batch * p.ho * p.wo;
+  for (const Measured3x3& m : kNativeFwd3x3S2)
+    p.native |= m.batch == batch && m.h == h && m.w == w && m.c == c && m.n == n;
+  p.ntiles = p.n / p.bn;
+  p.nchunks = p.c / p.kc;
+  p.row_tiles = (p.rows + p.tile_rows - 1) / p.tile_rows;
+  const int halo[4] = {0, 1, p.wo, p.wo + 1};
+  for (int pl = 0, base = 0; pl < 4; pl++) {
+    p.plane_base[pl] = base;
+    p.plane_rows[pl] = p.tile_rows + halo[pl];
+    base += p.plane_rows[pl];
+  }
+  p.strip_rows = (int)strip;
+  p.xvecs = (p.strip_rows + 63) / 64;
+  p.magic_wo = p.wo == 1 ? 0u : (unsigned)(((1ull << 32) + p.wo - 1) / p.wo);
+  p.magic_ho = p.ho == 1 ? 0u : (unsigned)(((1ull << 32) + p.ho - 1) / p.ho);
+
+  // conv3x3_fwd_plan's grid: one workgroup per CU
+  int64_t splits = std::min<int64_t>(p.row_tiles, std::max(1, kConvCus / p.ntiles));
+  if (max_workgroups > 0)
+    splits = std::min(splits, std::max<int64_t>(
+                                  1, std::min<int64_t>(max_workgroups, 1 << 20) /
+                                         p.ntiles));
+  if (splits > 8) splits -= splits % 8;  // conv3x3_fwd_split
+  p.splits = (int)splits;
+  p.grid = p.ntiles * p.splits;
+  p.tiles_per_split = (p.row_tiles + p.splits - 1) / p.splits;
+  p.run = 16 * p.tiles_per_split;
   p.lds_bytes = 2 * kConv3x3FwdWBytes + 2 * p.xvecs * 64 * p.kc * 2 +
                 kConvStageBytes;
   p.pstride = 2 * p.n + p.ntiles;

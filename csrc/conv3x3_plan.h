@@ -288,6 +288,93 @@ __host__ __device__ inline unsigned conv3x3_fwd_taps(const Conv3x3FwdPlan& p,
 void launch_conv3x3_stats(const Conv3x3FwdPlan& p, const void* x, const void* w,
                           void* y, float* part, hipStream_t stream);
 
+// ---- stride-2 forward with BatchNorm partials (conv3x3s2_stats) --------------
+//
+// The same GEMM for a 3x3 / stride 2 / padding 1 convolution of an image with
+// even H and W: R = B*Ho*Wo output pixels in memory order, Ho = H/2, Wo = W/2.
+// Output pixel (oh, ow) and tap (r, s) read input (2*oh + r - 1, 2*ow + s - 1),
+// so consecutive output pixels have neighbours two input pixels apart and one
+// strip with an offset per tap no longer serves.  The strip of a tile is four
+// parity planes instead: entry m = (b, oh, ow) of plane (pr, pc) holds input
+// pixel (b, 2*oh + pr, 2*ow + pc).  r == 1 is the even row of oh, r == 2 the
+// odd row of oh and r == 0 the odd row of oh - 1, columns alike, so tap (r, s)
+// of tile row m is entry m - (r == 0)*Wo - (s == 0) of plane (r != 1, s != 1):
+// the nine taps again differ by an LDS base and offset.  Plane (1, 1) serves
+// four taps and has a halo of Wo + 1 entries before the tile, (1, 0) two taps
+// and Wo, (0, 1) two taps and 1, (0, 0) the centre tap and none.  Every input
+// pixel of a tile's footprint is in exactly one plane and is loaded once.
+//
+// There are no zero pads.  An entry outside the tensor holds the entry nearest
+// inside, and with even H and W only r == 0 (needs oh > 0) and s == 0 (needs
+// ow > 0) can leave the image: the lane clears those operands in registers.
+//
+// A tile is 128 output pixels, wave w rows 32*w .. 32*w+31 with all 64
+// channels, and a stage one 32-channel chunk of it: 4*128 + 2*Wo + 2 entries
+// of 64 bytes.  With the two [9][64][32] weight chunks (72 KiB) and the
+// epilogue's stage (16 KiB) two strip buffers may take 36 KiB each, 576
+// entries, nine vectors a thread: Wo <= 31, W <= 62.  A 256-pixel tile would
+// need 68 KiB a buffer at Wo = 28 and not fit twice.  The weight is always
+// streamed (C == 64 is two chunks); grid, walk, moments and partials are
+// those of conv3x3_stats with 16 values per lane and tile.
+constexpr int kConv3x3S2TileRows = 128;
+// a thread's share of a strip, in 16-byte vectors: 64 entries each
+constexpr int kConv3x3S2XVecs = 9;
+
+struct Conv3x3S2FwdPlan : Conv3x3FwdPlan {  // h, w: the input's; rows: B*Ho*Wo
+  int ho = 0, wo = 0;
+  // plane 2*pr + pc: first entry in the strip, and entries (tile_rows + halo)
+  int plane_base[4] = {}, plane_rows[4] = {};
+  unsigned magic_wo = 0, magic_ho = 0;  // conv3x3s2_div; 0 where the divisor is 1
+};
+
+// C and N powers of two in [64, 512], H and W even, W <= 62, H <= 2048 (the
+// divisions below), 2 <= B*Ho*Wo and B*H*W <= kBnMaxRows.  `max_workgroups`
+// > 0 caps the grid.
+Conv3x3S2FwdPlan conv3x3s2_fwd_plan(int64_t batch, int64_t h, int64_t w,
+                                    int64_t c, int64_t n,
+                                    int64_t max_workgroups = 0);
+
+// v / d for v * d < 2^32 (v < 2^22 output rows, d <= 2^10), magic =
+// ceil(2^32 / d), which is 2^32 and stored as 0 at d == 1
+__host__ __device__ inline int conv3x3s2_div(int v, unsigned magic) {
+  return magic == 0
+             ? v
+             : (int)(((unsigned long long)(unsigned)v * magic) >> 32);
+}
+// The input pixel (b*H + ih)*W + iw that entry e of tile t's strip holds.
+__host__ __device__ inline int conv3x3s2_fwd_strip_pixel(
+    const Conv3x3S2FwdPlan& p, int t, int e) {
+  const int pl = (e >= p.plane_base[1]) + (e >= p.plane_base[2]) +
+                 (e >= p.plane_base[3]);
+  int m = t * kConv3x3S2TileRows - (p.plane_rows[pl] - kConv3x3S2TileRows) +
+          (e - p.plane_base[pl]);
+  m = m < 0 ? 0 : m < p.rows ? m : p.rows - 1;
+  const int line = conv3x3s2_div(m, p.magic_wo), ow = m - line * p.wo;
+  return (2 * line + (pl >> 1)) * p.w + 2 * ow + (pl & 1);
+}
+// The strip entry that tap = 3r + s of tile row m reads.
+__host__ __device__ inline int conv3x3s2_fwd_strip_index(
+    const Conv3x3S2FwdPlan& p, int m, int tap) {
+  const int r = tap / 3, s = tap % 3, pl = 2 * (r != 1) + (s != 1);
+  return p.plane_base[pl] + (p.plane_rows[pl] - kConv3x3S2TileRows) + m -
+         (r == 0 ? p.wo : 0) - (s == 0 ? 1 : 0);
+}
+// Bit 3r + s is set where output pixel `row` has its neighbour
+// (2*oh + r - 1, 2*ow + s - 1) in its own image.
+__host__ __device__ inline unsigned conv3x3s2_fwd_taps(
+    const Conv3x3S2FwdPlan& p, int row) {
+  const int line = conv3x3s2_div(row, p.magic_wo), ow = row - line * p.wo;
+  const int oh = line - conv3x3s2_div(line, p.magic_ho) * p.ho;
+  const unsigned cols = (ow > 0 ? 1u : 0u) | 6u;
+  return (oh > 0 ? cols : 0u) | cols << 3 | cols << 6;
+}
+
+// y[B, Ho, Wo, N] bf16 and part[splits, pstride] fp32 from x[B, H, W, C] and
+// w[N, 3, 3, C] bf16; every pointer 16-byte aligned.
+void launch_conv3x3s2_stats(const Conv3x3S2FwdPlan& p, const void* x,
+                            const void* w, void* y, float* part,
+                            hipStream_t stream);
+
 // ---- input gradient (conv3x3_bwd_data) ----------------------------------------
 //
 // dX[R, C] = sum over the nine taps t of dY_t[R, N] * W_{8-t}[N, C]: the

@@ -63,7 +63,12 @@ depends on none of them.  ``conv3x3_bn_act(conv, bn, x)`` is
 does; ``CGX_NATIVE_CONV3X3`` switches it, on its own.  The input gradient of
 both has the forward's implicit GEMM with the taps mirrored and the weight
 read transposed (``_C.conv3x3_bwd_data``); ``CGX_NATIVE_CONV3X3_BWD`` switches
-it, on its own as well.
+it, on its own as well.  The three 3x3 / stride 2 / padding 1 convolutions
+(``conv2`` of the first block of ``layer2..4``) have a native forward of their
+own, ``_C.conv3x3s2_stats``, which de-interleaves the input into four parity
+planes in LDS and hands ``bn`` its statistics likewise;
+``CGX_NATIVE_CONV3X3_S2`` switches it, on its own, and their backward is the
+stock one.
 
 ``conv_stem_bn_act_pool(conv, bn, x, pool)`` is
 ``bn_act_pool(bn, conv(x), pool)`` for the stem, ``Conv2d(3, 64, 7, stride=2,
@@ -532,26 +537,51 @@ def native_conv3x3_bwd_mode() -> str:
     return os.environ.get("CGX_NATIVE_CONV3X3_BWD", "1")
 
 
-def _conv3x3(conv, x, bn=None):
-    """``(conv(x), part)``.  For a bias-free 3x3 / stride 1 / padding 1
-    convolution of a channels_last bf16 CUDA activation it goes through
-    ``_Conv3x3`` where the native forward (only with a training ``bn`` to
-    take its partials), the native weight gradient or the native input
-    gradient is to run, each by its own switch and its plan's table; in every
-    other case it is the module call itself and ``part`` is None."""
-    fwd_mode = native_conv3x3_mode() if bn is not None else "0"
-    wrw_mode = native_conv3x3_wrw_mode() if torch.is_grad_enabled() else "0"
-    bwd_mode = native_conv3x3_bwd_mode() if torch.is_grad_enabled() else "0"
-    if fwd_mode == "0" and wrw_mode == "0" and bwd_mode == "0":
-        return conv(x), None
+def native_conv3x3_s2_mode() -> str:
+    """``CGX_NATIVE_CONV3X3_S2``, the switch of the stride-2 forward with
+    statistics (``_C.conv3x3s2_stats``), with the values of
+    ``CGX_NATIVE_CONV3X3_WRW``.  Off where ``CGX_FUSED_BN`` is; no other
+    switch reaches it."""
+    if not fused_bn_enabled():
+        return "0"
+    return os.environ.get("CGX_NATIVE_CONV3X3_S2", "1")
+
+
+class _Conv3x3S2(torch.autograd.Function):
+    """``(y, part) = f(x, weight)``: ``conv2d(x, weight, stride=2,
+    padding=1)`` by ``_C.conv3x3s2_stats`` with the BatchNorm partials of
+    ``y``; the backward is the stock one."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
+    def forward(ctx, x, weight):
+        ctx.save_for_backward(x, weight)
+        y, part = _C.conv3x3s2_stats(x, weight)
+        ctx.mark_non_differentiable(part)
+        return y, part
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dy, _dpart):
+        x, weight = ctx.saved_tensors
+        dx, dw, _ = torch.ops.aten.convolution_backward(
+            dy, x, weight, None, (2, 2), (1, 1), (1, 1), False, (0, 0), 1,
+            (ctx.needs_input_grad[0], ctx.needs_input_grad[1], False))
+        return dx, dw
+
+
+def _conv3x3_weight(conv, x, stride):
+    """The weight of a bias-free 3x3 / padding 1 convolution of that stride
+    on a channels_last bf16 CUDA activation, where a native kernel could take
+    the two, else None."""
     if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == (3, 3)
-            and conv.stride == (1, 1) and conv.padding == (1, 1)
+            and conv.stride == stride and conv.padding == (1, 1)
             and conv.dilation == (1, 1) and conv.groups == 1
             and conv.bias is None and conv.padding_mode == "zeros"):
-        return conv(x), None
+        return None
     if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16
             and _C.bn_eligible(x)):
-        return conv(x), None
+        return None
     w = conv.weight
     # under bf16 autocast the fp32 weight reaches the convolution as bf16
     autocast = (torch.is_autocast_enabled("cuda")
@@ -559,20 +589,58 @@ def _conv3x3(conv, x, bn=None):
     if not (w.device == x.device and w.shape[1] == x.shape[1]
             and (w.dtype == torch.bfloat16
                  or (autocast and w.dtype == torch.float32))):
+        return None
+    return w
+
+
+def _takes(mode, plan):
+    return mode != "0" and plan["eligible"] and (plan["native"]
+                                                 or mode == "all")
+
+
+def _conv3x3_s2(conv, x, bn):
+    """``_conv3x3`` for stride 2: through ``_Conv3x3S2`` where the native
+    forward is to run, which needs a training ``bn`` to take its partials."""
+    mode = native_conv3x3_s2_mode() if bn is not None else "0"
+    w = _conv3x3_weight(conv, x, (2, 2)) if mode != "0" else None
+    if w is None:
         return conv(x), None
     shape = (x.shape[0], x.shape[2], x.shape[3], x.shape[1], w.shape[0])
+    if not (_takes(mode, _C.conv3x3s2_fwd_plan(*shape))
+            and _native(bn, x, None)
+            and w.is_contiguous(memory_format=torch.channels_last)
+            and (w.dtype != torch.bfloat16
+                 or _C.conv3x3s2_fwd_eligible(x, w))):
+        return conv(x), None
+    return _Conv3x3S2.apply(x, w)
 
-    def takes(mode, plan):
-        return mode != "0" and plan["eligible"] and (plan["native"]
-                                                     or mode == "all")
 
+def _conv3x3(conv, x, bn=None):
+    """``(conv(x), part)``.  For a bias-free 3x3 / stride 1 / padding 1
+    convolution of a channels_last bf16 CUDA activation it goes through
+    ``_Conv3x3`` where the native forward (only with a training ``bn`` to
+    take its partials), the native weight gradient or the native input
+    gradient is to run, each by its own switch and its plan's table; in every
+    other case it is the module call itself and ``part`` is None.  Stride 2
+    has a forward only (``_conv3x3_s2``)."""
+    if getattr(conv, "stride", None) == (2, 2):
+        return _conv3x3_s2(conv, x, bn)
+    fwd_mode = native_conv3x3_mode() if bn is not None else "0"
+    wrw_mode = native_conv3x3_wrw_mode() if torch.is_grad_enabled() else "0"
+    bwd_mode = native_conv3x3_bwd_mode() if torch.is_grad_enabled() else "0"
+    if fwd_mode == "0" and wrw_mode == "0" and bwd_mode == "0":
+        return conv(x), None
+    w = _conv3x3_weight(conv, x, (1, 1))
+    if w is None:
+        return conv(x), None
+    shape = (x.shape[0], x.shape[2], x.shape[3], x.shape[1], w.shape[0])
     # the cast of a weight keeps its strides: the kernel wants [N][3][3][C]
-    fwd = (takes(fwd_mode, _C.conv3x3_fwd_plan(*shape))
+    fwd = (_takes(fwd_mode, _C.conv3x3_fwd_plan(*shape))
            and _native(bn, x, None)
            and w.is_contiguous(memory_format=torch.channels_last)
            and (w.dtype != torch.bfloat16 or _C.conv3x3_fwd_eligible(x, w)))
-    wrw = w.requires_grad and takes(wrw_mode, _C.conv3x3_wrw_plan(*shape))
-    bwd = x.requires_grad and takes(bwd_mode, _C.conv3x3_bwd_plan(*shape))
+    wrw = w.requires_grad and _takes(wrw_mode, _C.conv3x3_wrw_plan(*shape))
+    bwd = x.requires_grad and _takes(bwd_mode, _C.conv3x3_bwd_plan(*shape))
     if not (fwd or wrw or bwd):
         return conv(x), None
     return _Conv3x3.apply(x, w, fwd, wrw, bwd)
