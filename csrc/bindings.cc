@@ -1878,6 +1878,93 @@ py::dict py_conv3x3_bwd_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
       conv3x3_bwd_plan(batch, h, w, c, n, max_workgroups));
 }
 
+// ---- 3x3 / stride 2 convolution input gradient --------------------------------
+
+// dy [B, N, Ho, Wo] -> the plan of dx [B, C, 2*Ho, 2*Wo]
+Conv3x3S2BwdPlan conv3x3s2_bwd_plan_of(const at::Tensor& dy,
+                                       const at::Tensor& w,
+                                       int64_t max_workgroups = 0) {
+  return conv3x3s2_bwd_plan(dy.size(0), 2 * dy.size(2), 2 * dy.size(3),
+                            w.size(1), w.size(0), max_workgroups);
+}
+
+// the tensors of py_conv3x3_bwd_eligible
+bool py_conv3x3s2_bwd_eligible(const at::Tensor& dy, const at::Tensor& w) {
+  return bn_tensor_ok(dy) && w.is_cuda() && w.device() == dy.device() &&
+         w.scalar_type() == at::kBFloat16 && w.dim() == 4 && w.size(2) == 3 &&
+         w.size(3) == 3 && w.size(0) == dy.size(1) &&
+         w.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+         reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0 &&
+         conv3x3s2_bwd_plan_of(dy, w).eligible;
+}
+
+// the input gradient of conv2d(x, weight, stride=2, padding=1), x with even
+// sides, from the gradient dy of its output
+at::Tensor py_conv3x3s2_bwd_data(const at::Tensor& dy, const at::Tensor& weight,
+                                 int64_t max_workgroups) {
+  TORCH_CHECK(max_workgroups >= 0, "conv3x3s2_bwd_data: max_workgroups >= 0");
+  TORCH_CHECK(py_conv3x3s2_bwd_eligible(dy, weight),
+              "conv3x3s2_bwd_data: dy or weight is not eligible");
+  const Conv3x3S2BwdPlan p = conv3x3s2_bwd_plan_of(dy, weight, max_workgroups);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dy.device().index());
+  auto dx = at::empty({dy.size(0), weight.size(1), p.h, p.w}, dy.options(),
+                      at::MemoryFormat::ChannelsLast);
+  launch_conv3x3s2_bwd_data(p, dy.data_ptr(), weight.data_ptr(), dx.data_ptr(),
+                            bn_stream(dy));
+  return dx;
+}
+
+// conv3x3_bwd_plan's keys (rows are those of dy), and the size of dy
+py::dict py_conv3x3s2_bwd_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
+                               int64_t n, int64_t max_workgroups) {
+  const Conv3x3S2BwdPlan p =
+      conv3x3s2_bwd_plan(batch, h, w, c, n, max_workgroups);
+  py::dict d = conv3x3_fwd_plan_dict(p);
+  d["ho"] = p.ho;
+  d["wo"] = p.wo;
+  return d;
+}
+
+at::Tensor conv3x3_fwd_walk_of(const Conv3x3FwdPlan& p);  // below
+at::Tensor py_conv3x3s2_bwd_walk(int64_t batch, int64_t h, int64_t w,
+                                 int64_t c, int64_t n,
+                                 int64_t max_workgroups) {
+  return conv3x3_fwd_walk_of(
+      conv3x3s2_bwd_plan(batch, h, w, c, n, max_workgroups));
+}
+
+// Test seam: entry [row, class, term] holds (weight tap 3r + s, dY row, dX
+// pixel) of the product the kernel adds to class `class` of dY row `row`: the
+// dY row read through the strip of the row's tile, -1 where the operand is
+// cleared, and all three -1 where the class has fewer terms.
+at::Tensor py_conv3x3s2_bwd_terms(int64_t batch, int64_t h, int64_t w,
+                                  int64_t c, int64_t n) {
+  const Conv3x3S2BwdPlan p = conv3x3s2_bwd_plan(batch, h, w, c, n);
+  TORCH_CHECK(p.eligible, "conv3x3s2_bwd_terms: shape is not eligible");
+  auto out = at::full({p.rows, 4, 4, 3}, -1,
+                      at::TensorOptions().dtype(at::kLong));
+  int64_t* o = out.data_ptr<int64_t>();
+  for (int row = 0; row < p.rows; row++) {
+    const unsigned valid = conv3x3s2_bwd_valid(p, row);
+    const int t = row / p.tile_rows, m = row % p.tile_rows;
+    for (int cls = 0; cls < 4; cls++)
+      for (int term = 0; term < 4; term++) {
+        const Conv3x3S2BwdTerm tm = conv3x3s2_bwd_term(cls, term);
+        if (tm.tap < 0) continue;
+        const int i = conv3x3s2_bwd_strip_index(p, m, tm.shift);
+        TORCH_CHECK(i >= 0 && i < p.strip_rows,
+                    "conv3x3s2_bwd_terms: off the strip");
+        int64_t* e = o + (((int64_t)row * 4 + cls) * 4 + term) * 3;
+        e[0] = tm.tap;
+        e[1] = (valid & tm.shift) == (unsigned)tm.shift
+                   ? conv3x3s2_bwd_strip_row(p, t, i)
+                   : -1;
+        e[2] = conv3x3s2_bwd_pixel(p, row, cls);
+      }
+  }
+  return out;
+}
+
 // Test seam: the kernel's walk replayed on the host.  Entry [wg, i] holds
 // (n0, split, row0, row1) of the i-th tile of workgroup wg, -1 once it has
 // run out of tiles.
@@ -2472,6 +2559,33 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Test seam: [rows, 9] int64, the input pixel each tap of each output "
         "pixel reads through its tile's planes, -1 where the operand is "
         "cleared.");
+  m.def("conv3x3s2_bwd_data", &cgx::py_conv3x3s2_bwd_data, py::arg("dy"),
+        py::arg("weight"), py::arg("max_workgroups") = 0,
+        "Input gradient of conv2d(x, weight, stride=2, padding=1) of a 3x3 "
+        "convolution of an image with even sides by the native direct GEMM "
+        "-> dx [B, C, 2*Ho, 2*Wo], channels_last bf16; the weight is the "
+        "convolution's own [N, C, 3, 3].  max_workgroups > 0 caps the grid.");
+  m.def("conv3x3s2_bwd_eligible", &cgx::py_conv3x3s2_bwd_eligible,
+        py::arg("dy"), py::arg("weight"),
+        "True where conv3x3s2_bwd_data takes (dy, weight): as "
+        "conv3x3_bwd_eligible, with Wo <= 63 and Ho <= 1024.");
+  m.def("conv3x3s2_bwd_plan", &cgx::py_conv3x3s2_bwd_plan, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("c"), py::arg("n"),
+        py::arg("max_workgroups") = 0,
+        "The launch geometry of conv3x3s2_bwd_data for dx [batch, c, h, w] "
+        "from dy [batch, n, h/2, w/2], with the keys of conv3x3_bwd_plan "
+        "(rows are those of dy), and `native`: whether the model uses it for "
+        "this problem.");
+  m.def("conv3x3s2_bwd_walk", &cgx::py_conv3x3s2_bwd_walk, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("c"), py::arg("n"),
+        py::arg("max_workgroups") = 0,
+        "Test seam: conv3x3_fwd_walk for conv3x3s2_bwd_data, n0 a channel of "
+        "dx and the rows those of dy.");
+  m.def("conv3x3s2_bwd_terms", &cgx::py_conv3x3s2_bwd_terms, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("c"), py::arg("n"),
+        "Test seam: [rows, 4 classes, 4 terms, 3] int64, (weight tap, dY row "
+        "read through the strip or -1 where cleared, dX pixel) of every "
+        "product of conv3x3s2_bwd_data; -1 where a class has fewer terms.");
   m.def("conv_stem_stats", &cgx::py_conv_stem_stats, py::arg("x"),
         py::arg("weight"), py::arg("max_workgroups") = 0,
         "conv2d(x, weight, stride=2, padding=3) of the 3 -> 64 channel 7x7 "

@@ -1,9 +1,10 @@
 // The 3x3 / stride 1 / padding 1 convolution on channels_last bf16 tensors as
 // implicit GEMMs: the weight gradient (conv3x3_wrw, first), the forward that
 // also produces BatchNorm partials (conv3x3_stats, below it) and the input
-// gradient (conv3x3_bwd_data, last), each with its own description; between
+// gradient (conv3x3_bwd_data), each with its own description; between
 // the last two the forward of the 3x3 / stride 2 / padding 1 convolution
-// (conv3x3s2_stats).  Geometry: conv3x3_plan.h.
+// (conv3x3s2_stats) and last its input gradient (conv3x3s2_bwd_data).
+// Geometry: conv3x3_plan.h.
 //
 // dW[n][(3r+s)*C + c] = sum over pixels of dY[b, h, w, n] * X[b, h+r-1, w+s-1, c].
 // Both operands have the contracted index slow, so both MFMA operands are
@@ -1187,7 +1188,247 @@ void launch_bwd3x3(const Conv3x3FwdPlan& p, const void* dy, const void* w,
   CGX_HIP_CHECK(hipGetLastError());
 }
 
+// ---- stride-2 input gradient --------------------------------------------------
+//
+// The input gradient of conv2d(x, w, stride 2, padding 1) of an image with
+// even sides, written directly: no zeros are inserted into dY and no MFMA
+// multiplies one.  Geometry and the four classes: Conv3x3S2BwdPlan.
+//
+//   A   the strip of a tile, rows 128*t .. 128*t + 128 + Wo of one 32-channel
+//       chunk of dY, 64 bytes an entry in the fwd_slot layout, no parity
+//       planes and no halo before the tile.  Lane (c, h) reads for shift k the
+//       16 bytes of entry m + c + (k & 1) + (k & 2 ? Wo : 0): 16 consecutive
+//       entries a pass, conflict-free at every start like the forwards'
+//       strips, and clears them where conv3x3s2_bwd_valid lacks a bit of k
+//   B   the [9 taps][32 n][64 c] chunk of conv3x3_bwd_data, unmirrored: class
+//       cls and shift k multiply tap conv3x3s2_bwd_term; read transposed with
+//       the same base address, the tap an immediate offset
+//   C   the four waves are 2 x 2 over a 128-row x 64-channel tile: a wave owns
+//       64 rows x 32 channels x four classes, 128 fp32 accumulators.  Per
+//       16-deep step it reads eight A operands (two sub-tiles x four shifts)
+//       and nine B operands for 18 MFMAs: 272 bytes of LDS a lane, against
+//       432 in conv3x3s2_stats and 288 in conv3x3_stats
+//
+// A stage is one chunk of one tile, 36 MFMAs a wave, staged through registers
+// behind the MFMAs of the stage before and ordered by one barrier, as in
+// conv3x3_stats; the weight is always streamed.  Every accumulator is one
+// chain over (chunk, step, term) in a fixed order: the same bits every run.
+//
+// Epilogue.  Row m of class (ph, pw) is dX pixel (2*line + ph)*W + 2b + pw,
+// line = m / Wo: consecutive rows are two pixels apart and the classes of a
+// row are a 2x2 cell, so no wave holds a run of pixels.  All four waves round
+// their accumulators into one image [4 classes][128 rows][64 channels] of
+// LDS, in the swizzle of fwd_store_subtile, and after a barrier the 256
+// threads write it out as 128-byte runs, one per pixel and channel tile,
+// eight lanes a run.  A thread serves four rows of the tile (the same for
+// every class), so a tile costs it four divisions.  The image is written
+// again only in the next tile's epilogue, at least two stage barriers later.
+
+static_assert(kConv3x3S2BwdTileRows == 2 * 64 &&
+              kConv3x3S2BwdStageBytes == 4 * kConv3x3S2BwdTileRows * 128);
+
+// the (class, term) pairs in the order a step issues them: no class twice in a
+// row, so that consecutive MFMAs do not wait for one another's result
+constexpr int kS2BwdOrder[9][2] = {{3, 0}, {1, 0}, {3, 1}, {2, 0}, {3, 2},
+                                   {1, 1}, {3, 3}, {2, 1}, {0, 0}};
+
+struct S2BwdStage {
+  u32x4 wv[kFwdWShare], xv[kConv3x3S2BwdXVecs];
+  __device__ __forceinline__ void load(const uint4* __restrict__ dy,
+                                       const uint4* __restrict__ w,
+                                       const Conv3x3S2BwdPlan& p, int c0,
+                                       int tile, int kc, int tid) {
+#pragma unroll
+    for (int i = 0; i < kFwdWShare; i++)
+      wv[i] = *reinterpret_cast<const u32x4*>(
+          bwd_w_src(w, p, c0, kc, tid + i * kT));
+#pragma unroll
+    for (int i = 0; i < kConv3x3S2BwdXVecs; i++)
+      if (i < p.xvecs) {  // uniform
+        const int idx = tid + i * kT;
+        const int64_t r = conv3x3s2_bwd_strip_row(p, tile, idx >> 2);
+        xv[i] = *reinterpret_cast<const u32x4*>(
+            dy + (r * p.c + kc * kConv3x3FwdKc) / 8 + (idx & 3));
+      }
+  }
+  __device__ __forceinline__ void store(uint4* wb, uint4* xb,
+                                        const Conv3x3S2BwdPlan& p,
+                                        int tid) const {
+#pragma unroll
+    for (int i = 0; i < kFwdWShare; i++)
+      *reinterpret_cast<u32x4*>(wb + bwd_w_slot(tid + i * kT)) = wv[i];
+#pragma unroll
+    for (int i = 0; i < kConv3x3S2BwdXVecs; i++)
+      if (i < p.xvecs) {
+        const int idx = tid + i * kT;
+        *reinterpret_cast<u32x4*>(xb + fwd_slot(idx >> 2, idx & 3)) = xv[i];
+      }
+  }
+};
+
+__global__ __launch_bounds__(kT) void conv3x3s2_bwd_data(
+    const uint4* __restrict__ dy, const uint4* __restrict__ w,
+    uint4* __restrict__ dx, Conv3x3S2BwdPlan p) {
+  extern __shared__ uint4 lds[];
+  constexpr int BN = kConv3x3FwdBn, M = kConv3x3S2BwdTileRows;
+  constexpr int kTapBytes = kConv3x3FwdKc * BN * 2;  // [32 n][64 c]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int c = lane & 31, h = lane >> 5;
+  const int wr = wave >> 1, wc = wave & 1;  // the wave's rows and channels
+  const int c0 = conv3x3_fwd_ntile(p, blockIdx.x) * BN;  // of dX's channels
+  const int split = conv3x3_fwd_split(p, blockIdx.x);
+  const int nvec = p.n / 8;
+  const int xbuf = p.xvecs * kT;      // vectors of a strip buffer
+  uint4* wimg = lds;                  // two weight chunks
+  uint4* ximg = lds + 2 * kFwdWVecs;  // two strips
+  uint4* stage = ximg + 2 * xbuf;     // [4 classes][128 rows][64 channels]
+
+  S2BwdStage st;
+  int tile = split, kc = 0, buf = 0;  // split < row_tiles
+  st.load(dy, w, p, c0, tile, 0, tid);
+  st.store(wimg, ximg, p, tid);
+
+  // the lane's B base, as conv3x3_bwd_data, for the wave's 32 channels ...
+  const int bb = wrw_cell<BN>(8 * h + ((lane >> 2) & 3), wc) +
+                 32 * ((lane >> 4) & 1) + 8 * (lane & 3);
+  // ... and the strip entry of each shift for its row of each sub-tile, the
+  // same on every tile
+  int at[2][4];
+#pragma unroll
+  for (int s = 0; s < 2; s++)
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      at[s][k] = conv3x3s2_bwd_strip_index(p, wr * 64 + s * 32 + c, k);
+
+  f32x16 acc[4][2];  // [class][sub-tile]
+#pragma unroll
+  for (int cls = 0; cls < 4; cls++)
+#pragma unroll
+    for (int s = 0; s < 2; s++)
+#pragma unroll
+      for (int e = 0; e < 16; e++) acc[cls][s][e] = 0.f;
+  unsigned valid[2] = {0, 0};
+
+  while (tile < p.row_tiles) {
+    // as conv3x3_stats: the next stage is loaded before the MFMAs of this one
+    int nkc = kc + 1, ntl = tile;
+    if (nkc == p.nchunks) nkc = 0, ntl = tile + p.splits;
+    const bool more = ntl < p.row_tiles;
+    if (more) st.load(dy, w, p, c0, ntl, nkc, tid);
+    // buffer `buf` is written, and the other one, read a stage ago, is free
+    __syncthreads();
+    if (kc == 0) {
+#pragma unroll
+      for (int s = 0; s < 2; s++)
+        valid[s] = conv3x3s2_bwd_valid(p, tile * M + wr * 64 + s * 32 + c);
+    }
+    char* wl = reinterpret_cast<char*>(wimg + buf * kFwdWVecs);
+    const uint4* xl = ximg + buf * xbuf;
+    uint4 av[2][2][4];  // [step][sub-tile][shift]
+    bf16x8 bv[2];       // the B operand of this unit and the next
+    auto read_a = [&](int step, int i) {  // operand i = 4*s + k of a step
+      const int s = i >> 2, k = i & 3;
+      const uint4 v = xl[fwd_slot(at[s][k], 2 * step + h)];
+      const unsigned m = (valid[s] & k) == (unsigned)k ? ~0u : 0u;
+      av[step][s][k] = make_uint4(v.x & m, v.y & m, v.z & m, v.w & m);
+    };
+    auto read_b = [&](int u) {  // unit u = 9*step + position in the order
+      const int step = u / 9, i = u % 9;
+      const int tap =
+          conv3x3s2_bwd_term(kS2BwdOrder[i][0], kS2BwdOrder[i][1]).tap;
+      bv[u & 1] = wrw_operand<BN>(wl + tap * kTapBytes, bb, step);
+    };
+#pragma unroll
+    for (int i = 0; i < 8; i++) read_a(0, i);
+    read_b(0);
+#pragma unroll
+    for (int u = 0; u < 18; u++) {
+      if (u + 1 < 18) read_b(u + 1);
+      if (u < 8) read_a(1, u);  // the second step's A behind the first's MFMAs
+      const int step = u / 9, i = u % 9, cls = kS2BwdOrder[i][0];
+      const int k = conv3x3s2_bwd_term(cls, kS2BwdOrder[i][1]).shift;
+#pragma unroll
+      for (int s = 0; s < 2; s++)
+        acc[cls][s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            __builtin_bit_cast(bf16x8, av[step][s][k]), bv[u & 1], acc[cls][s],
+            0, 0, 0);
+    }
+    // nothing that waits for the loads above may move up among the MFMAs
+    __builtin_amdgcn_sched_barrier(0);
+    buf ^= 1;
+    if (more) st.store(wimg + buf * kFwdWVecs, ximg + buf * xbuf, p, tid);
+
+    if (nkc == 0) {  // the tile is complete: round once, gather, store
+      unsigned* stage32 = reinterpret_cast<unsigned*>(stage);
+      const int odd = c & 1;
+#pragma unroll
+      for (int cls = 0; cls < 4; cls++)
+#pragma unroll
+        for (int s = 0; s < 2; s++)
+#pragma unroll
+          for (int e = 0; e < 8; e++) {
+            // as fwd_store_subtile: lanes c and c^1 trade words, so that the
+            // even lane writes channels (c, c+1) of row 2e and the odd one
+            // channels (c-1, c) of row 2e+1
+            const unsigned own =
+                fwd_pack_bf16(acc[cls][s][2 * e], acc[cls][s][2 * e + 1]);
+            const unsigned other = (unsigned)__builtin_amdgcn_update_dpp(
+                0, (int)own, 0xB1, 0xf, 0xf, false);  // quad_perm [1, 0, 3, 2]
+            const unsigned word = odd ? (other >> 16) | (own & 0xffff0000u)
+                                      : (own & 0xffffu) | (other << 16);
+            const int row =
+                cls * M + wr * 64 + s * 32 + acc_row(2 * e, h) + odd;
+            stage32[row * 32 + ((wc * 16 + (c >> 1)) ^ ((row & 1) << 4))] = word;
+            acc[cls][s][2 * e] = 0.f, acc[cls][s][2 * e + 1] = 0.f;
+          }
+      // the thread's four rows of the tile: their cells' first pixels
+      int pix[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const int row = tile * M + j * 32 + (tid >> 3);
+        pix[j] = row < p.rows ? conv3x3s2_bwd_pixel(p, row, 0) : -1;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < 16; u++) {
+        const int idx = u * kT + tid, row = idx >> 3, q = idx & 7;
+        const int cls = u >> 2, px = pix[u & 3];
+        const uint4 v = stage[row * 8 + (q ^ ((row & 1) << 2))];
+        if (px >= 0)
+          dx[(int64_t)(px + (cls >> 1) * p.w + (cls & 1)) * nvec + c0 / 8 + q] =
+              v;
+      }
+    }
+    kc = nkc, tile = ntl;
+  }
+}
+
+void launch_bwd3x3s2(const Conv3x3S2BwdPlan& p, const void* dy, const void* w,
+                     void* dx, hipStream_t stream) {
+  static const hipError_t attr = hipFuncSetAttribute(
+      reinterpret_cast<const void*>(&conv3x3s2_bwd_data),
+      hipFuncAttributeMaxDynamicSharedMemorySize, kConvLdsBytes);
+  CGX_HIP_CHECK(attr);
+  hipLaunchKernelGGL(conv3x3s2_bwd_data, dim3(p.grid), dim3(kT), p.lds_bytes,
+                     stream, static_cast<const uint4*>(dy),
+                     static_cast<const uint4*>(w), static_cast<uint4*>(dx), p);
+  CGX_HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace
+
+void launch_conv3x3s2_bwd_data(const Conv3x3S2BwdPlan& p, const void* dy,
+                               const void* w, void* dx, hipStream_t stream) {
+  TORCH_CHECK(p.eligible, "conv3x3s2_bwd_data: shape is not eligible");
+  TORCH_CHECK(p.bn == kConv3x3FwdBn && p.kc == kConv3x3FwdKc &&
+                  p.tile_rows == kConv3x3S2BwdTileRows &&
+                  p.xvecs <= kConv3x3S2BwdXVecs &&
+                  p.strip_rows == p.tile_rows + p.wo + 1 &&
+                  p.strip_rows <= 64 * p.xvecs && p.nchunks >= 2 &&
+                  p.splits <= p.row_tiles && p.lds_bytes <= kConvLdsBytes,
+              "conv3x3s2_bwd_data: plan and kernel disagree");
+  launch_bwd3x3s2(p, dy, w, dx, stream);
+}
 
 void launch_conv3x3_bwd_data(const Conv3x3FwdPlan& p, const void* dy,
                              const void* w, void* dx, hipStream_t stream) {

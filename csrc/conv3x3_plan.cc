@@ -1,8 +1,9 @@
-// Launch geometry of the 3x3 weight gradient, forward and input gradient: see
+// Launch geometry of the 3x3 weight gradient, forwards and input gradients: see
 // conv3x3_plan.h.
 #include "conv3x3_plan.h"
 
 #include <algorithm>
+#include <array>
 
 namespace cgx {
 namespace {
@@ -63,6 +64,15 @@ constexpr Measured3x3 kNativeBwd3x3[] = {
 constexpr Measured3x3 kNativeFwd3x3S2[] = {
     {256, 14, 14, 512, 512},
 };
+
+// The same rule for conv3x3s2_bwd_data against MIOpen's stride-2
+// backward-data alone (benchmarks/conv3x3_s2_bwd_shapes.py); batch, H, W, C of
+// dX, N of dY.  None of the three strided problems of ResNet-50 at batch 256
+// met it in both processes: the native medians are 20 and 15 us below the
+// stock ones at 128<-128 to 56x56 and 256<-256 to 28x28 and 3 us above at
+// 512<-512 to 14x14, but each had a native run slower than a stock run in
+// one process.  The table is empty and all three stay stock.
+constexpr std::array<Measured3x3, 0> kNativeBwd3x3S2 = {};
 
 bool pow2_in(int64_t v, int64_t lo, int64_t hi) {
   return v >= lo && v <= hi && (v & (v - 1)) == 0;
@@ -341,6 +351,48 @@ Conv3x3FwdPlan conv3x3_bwd_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
   if (!p.eligible) return p;
   for (const Measured3x3& m : kNativeBwd3x3)
     p.native |= m.batch == batch && m.h == h && m.w == w && m.c == c && m.n == n;
+  return p;
+}
+
+Conv3x3S2BwdPlan conv3x3s2_bwd_plan(int64_t batch, int64_t h, int64_t w,
+                                    int64_t c, int64_t n,
+                                    int64_t max_workgroups) {
+  Conv3x3S2BwdPlan p;
+  p.bn = kConv3x3FwdBn;
+  p.tile_rows = kConv3x3S2BwdTileRows;
+  p.kc = kConv3x3FwdKc;
+  const int64_t strip = p.tile_rows + w / 2 + 1;  // the last row's shift Wo + 1
+  p.eligible = pow2_in(c, 64, 512) && pow2_in(n, 64, 512) && batch >= 1 &&
+               h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0 && h <= 2048 &&
+               batch <= kBnMaxRows && batch * h * w <= kBnMaxRows &&
+               batch * h * w >= 8 && strip <= 64 * kConv3x3S2BwdXVecs;
+  if (!p.eligible) return p;
+  // the exchanged problem, as conv3x3_bwd_plan
+  p.batch = (int)batch, p.h = (int)h, p.w = (int)w, p.c = (int)n, p.n = (int)c;
+  p.ho = p.h / 2, p.wo = p.w / 2;
+  p.rows = p.batch * p.ho * p.wo;
+  for (const Measured3x3& m : kNativeBwd3x3S2)
+    p.native |= m.batch == batch && m.h == h && m.w == w && m.c == c && m.n == n;
+  p.ntiles = p.n / p.bn;
+  p.nchunks = p.c / p.kc;
+  p.row_tiles = (p.rows + p.tile_rows - 1) / p.tile_rows;
+  p.strip_rows = (int)strip;
+  p.xvecs = (p.strip_rows + 63) / 64;
+  p.magic_wo = p.wo == 1 ? 0u : (unsigned)(((1ull << 32) + p.wo - 1) / p.wo);
+  p.magic_ho = p.ho == 1 ? 0u : (unsigned)(((1ull << 32) + p.ho - 1) / p.ho);
+
+  // conv3x3_fwd_plan's grid: one workgroup per CU
+  int64_t splits = std::min<int64_t>(p.row_tiles, std::max(1, kConvCus / p.ntiles));
+  if (max_workgroups > 0)
+    splits = std::min(splits, std::max<int64_t>(
+                                  1, std::min<int64_t>(max_workgroups, 1 << 20) /
+                                         p.ntiles));
+  if (splits > 8) splits -= splits % 8;  // conv3x3_fwd_split
+  p.splits = (int)splits;
+  p.grid = p.ntiles * p.splits;
+  p.tiles_per_split = (p.row_tiles + p.splits - 1) / p.splits;
+  p.lds_bytes = 2 * kConv3x3FwdWBytes + 2 * p.xvecs * 64 * p.kc * 2 +
+                kConv3x3S2BwdStageBytes;
   return p;
 }
 

@@ -1,7 +1,8 @@
 // Launch geometry of the weight gradient of a 3x3 / stride 1 / padding 1
 // convolution (conv3x3_wrw in conv3x3_kernels.hip) and, further down, of its
 // forward with BatchNorm partials (conv3x3_stats) and of its input gradient
-// (conv3x3_bwd_data).
+// (conv3x3_bwd_data); between them the stride-2 forward (conv3x3s2_stats) and
+// last the stride-2 input gradient (conv3x3s2_bwd_data).
 //
 // Pure host arithmetic, like conv1x1_plan.h.  dW[n, c, r, s] = sum over b, h, w
 // of dY[b, n, h, w] * X[b, c, h+r-1, w+s-1] on channels_last bf16 tensors is
@@ -392,5 +393,102 @@ Conv3x3FwdPlan conv3x3_bwd_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
 // convolution's own weight, read transposed; every pointer 16-byte aligned.
 void launch_conv3x3_bwd_data(const Conv3x3FwdPlan& p, const void* dy,
                              const void* w, void* dx, hipStream_t stream);
+
+// ---- stride-2 input gradient (conv3x3s2_bwd_data) -----------------------------
+//
+// dX[b, c, ih, iw] = sum over n, r, s of dY[b, n, oh, ow] * W[n, c, r, s] with
+// 2*oh = ih + 1 - r and 2*ow = iw + 1 - s: the input gradient of the 3x3 /
+// stride 2 / padding 1 convolution of an image with even H and W.  Written
+// directly, without inserted zeros: with ih = 2a + ph, iw = 2b + pw the four
+// pixels of the 2x2 cell of dY row m = (image, a, b) are four classes
+// cls = 2*ph + pw, and a class sums the shifts k that are subsets of its bits,
+// shift k being dY row m + (k & 1) + (k & 2 ? Wo : 0):
+//
+//   class 0   W(1,1) dY[m]
+//   class 1   W(1,2) dY[m] + W(1,0) dY[m+1]
+//   class 2   W(2,1) dY[m] + W(0,1) dY[m+Wo]
+//   class 3   W(2,2) dY[m] + W(2,0) dY[m+1] + W(0,2) dY[m+Wo] + W(0,0) dY[m+Wo+1]
+//
+// Nine products per dY row, the convolution's real flops, into four
+// accumulator sets.  The GEMM rows are the R = B*Ho*Wo rows of dY in memory
+// order, a tile 128 of them, and its strip rows T*t .. T*t + T + Wo of one
+// 32-deep chunk of dY's channels: the four shifts differ by an LDS offset.
+// Shift bit 0 needs b + 1 < Wo and bit 1 needs a + 1 < Ho, two validity bits a
+// row, and the lane clears the operand in registers; an entry past the tensor
+// holds the last row and is only ever reached with its bit clear.  With even H
+// and W every pixel of dX belongs to exactly one (row, class): each is
+// written once, with no fill and no second pass.
+//
+// The plan keeps conv3x3_bwd_plan's meaning of the fields: `c` is the
+// contraction depth, the N of dY, and `n` the output width, the C of dX; h
+// and w are dX's, rows is R.  LDS holds the two [9][32 n][64 c] weight chunks
+// of conv3x3_bwd_data (72 KiB), the whole rounded output of a tile, four
+// classes of [128][64] bf16 (64 KiB), from which 128-byte runs go to dX, and
+// two strip buffers in the 24 KiB that remain: three vectors a thread, 192
+// entries, Wo <= 63.  So LDS, through the output stage, bounds the width:
+// W <= 126.
+constexpr int kConv3x3S2BwdTileRows = 128;
+// a thread's share of a strip, in 16-byte vectors: 64 entries each
+constexpr int kConv3x3S2BwdXVecs = 3;
+// bytes of the output stage: [4 classes][128 rows][64 channels] bf16
+constexpr int kConv3x3S2BwdStageBytes = 4 * kConv3x3S2BwdTileRows * 64 * 2;
+
+struct Conv3x3S2BwdPlan : Conv3x3FwdPlan {
+  int ho = 0, wo = 0;
+  unsigned magic_wo = 0, magic_ho = 0;  // conv3x3s2_div
+};
+
+// C and N powers of two in [64, 512], H and W even, W <= 126, H <= 2048 (the
+// divisions), 2 <= B*Ho*Wo and B*H*W <= kBnMaxRows.  `max_workgroups` > 0
+// caps the grid.  `native` comes from a table of its own.
+Conv3x3S2BwdPlan conv3x3s2_bwd_plan(int64_t batch, int64_t h, int64_t w,
+                                    int64_t c, int64_t n,
+                                    int64_t max_workgroups = 0);
+
+// The dY row that entry i of tile t's strip holds.
+__host__ __device__ inline int conv3x3s2_bwd_strip_row(
+    const Conv3x3S2BwdPlan& p, int t, int i) {
+  const int r = t * kConv3x3S2BwdTileRows + i;
+  return r < p.rows ? r : p.rows - 1;
+}
+// The strip entry that shift k of tile row m reads.
+__host__ __device__ inline int conv3x3s2_bwd_strip_index(
+    const Conv3x3S2BwdPlan& p, int m, int k) {
+  return m + (k & 1) + (k & 2 ? p.wo : 0);
+}
+// Bit 0 is set where dY row `row` has a right neighbour in its image row, bit
+// 1 where it has a neighbour below in its image: shift k is valid where
+// (bits & k) == k.
+__host__ __device__ inline unsigned conv3x3s2_bwd_valid(
+    const Conv3x3S2BwdPlan& p, int row) {
+  const int line = conv3x3s2_div(row, p.magic_wo), b = row - line * p.wo;
+  const int a = line - conv3x3s2_div(line, p.magic_ho) * p.ho;
+  return (b + 1 < p.wo ? 1u : 0u) | (a + 1 < p.ho ? 2u : 0u);
+}
+// Term `term` of class cls: its shift k, the term-th subset of the class's
+// bits in ascending order, and the weight tap 3r + s it multiplies; tap -1
+// where the class has fewer terms.
+struct Conv3x3S2BwdTerm {
+  int tap, shift;
+};
+__host__ __device__ constexpr Conv3x3S2BwdTerm conv3x3s2_bwd_term(int cls,
+                                                                  int term) {
+  const int k = cls == 2 ? 2 * term : term;
+  if (term < 0 || k > 3 || (k & cls) != k) return {-1, 0};
+  const int r = cls & 2 ? (k & 2 ? 0 : 2) : 1;
+  const int s = cls & 1 ? (k & 1 ? 0 : 2) : 1;
+  return {3 * r + s, k};
+}
+// The pixel (image*H + ih)*W + iw of dX that class cls of dY row `row` is.
+__host__ __device__ inline int conv3x3s2_bwd_pixel(const Conv3x3S2BwdPlan& p,
+                                                   int row, int cls) {
+  const int line = conv3x3s2_div(row, p.magic_wo), b = row - line * p.wo;
+  return (2 * line + (cls >> 1)) * p.w + 2 * b + (cls & 1);
+}
+
+// dx[B, H, W, C] bf16 from dy[B, Ho, Wo, N] and w[N, 3, 3, C] bf16, the
+// convolution's own weight, read transposed; every pointer 16-byte aligned.
+void launch_conv3x3s2_bwd_data(const Conv3x3S2BwdPlan& p, const void* dy,
+                               const void* w, void* dx, hipStream_t stream);
 
 }  // namespace cgx

@@ -67,8 +67,11 @@ it, on its own as well.  The three 3x3 / stride 2 / padding 1 convolutions
 (``conv2`` of the first block of ``layer2..4``) have a native forward of their
 own, ``_C.conv3x3s2_stats``, which de-interleaves the input into four parity
 planes in LDS and hands ``bn`` its statistics likewise;
-``CGX_NATIVE_CONV3X3_S2`` switches it, on its own, and their backward is the
-stock one.
+``CGX_NATIVE_CONV3X3_S2`` switches it, on its own.  Their input gradient is
+native as well (``_C.conv3x3s2_bwd_data``): the four pixels of every 2x2 cell
+of dX are four sums over the rows of dY, nine products in all and none with an
+inserted zero; ``CGX_NATIVE_CONV3X3_S2_BWD`` switches it, on its own, and
+their weight gradient is the stock one.
 
 ``conv_stem_bn_act_pool(conv, bn, x, pool)`` is
 ``bn_act_pool(bn, conv(x), pool)`` for the stem, ``Conv2d(3, 64, 7, stride=2,
@@ -547,27 +550,51 @@ def native_conv3x3_s2_mode() -> str:
     return os.environ.get("CGX_NATIVE_CONV3X3_S2", "1")
 
 
+def native_conv3x3_s2_bwd_mode() -> str:
+    """``CGX_NATIVE_CONV3X3_S2_BWD``, the switch of the stride-2 input
+    gradient (``_C.conv3x3s2_bwd_data``), with the values of
+    ``CGX_NATIVE_CONV3X3_WRW``.  Off where ``CGX_FUSED_BN`` is; no other
+    switch reaches it, ``CGX_NATIVE_CONV3X3_S2`` and
+    ``CGX_NATIVE_CONV3X3_BWD`` included."""
+    if not fused_bn_enabled():
+        return "0"
+    return os.environ.get("CGX_NATIVE_CONV3X3_S2_BWD", "1")
+
+
 class _Conv3x3S2(torch.autograd.Function):
     """``(y, part) = f(x, weight)``: ``conv2d(x, weight, stride=2,
-    padding=1)`` by ``_C.conv3x3s2_stats`` with the BatchNorm partials of
-    ``y``; the backward is the stock one."""
+    padding=1)``, by ``_C.conv3x3s2_stats`` with the BatchNorm partials of
+    ``y`` where ``native_fwd`` says so, else stock with ``part`` None.  With
+    ``native_bwd`` the input gradient comes from ``_C.conv3x3s2_bwd_data``
+    where it takes the gradient that arrives; the stock backward computes
+    what remains, the weight gradient always."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
-    def forward(ctx, x, weight):
+    def forward(ctx, x, weight, native_fwd=True, native_bwd=False):
         ctx.save_for_backward(x, weight)
-        y, part = _C.conv3x3s2_stats(x, weight)
-        ctx.mark_non_differentiable(part)
-        return y, part
+        ctx.native_bwd = native_bwd
+        if native_fwd:
+            y, part = _C.conv3x3s2_stats(x, weight)
+            ctx.mark_non_differentiable(part)
+            return y, part
+        return F.conv2d(x, weight, stride=2, padding=1), None
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, dy, _dpart):
         x, weight = ctx.saved_tensors
-        dx, dw, _ = torch.ops.aten.convolution_backward(
-            dy, x, weight, None, (2, 2), (1, 1), (1, 1), False, (0, 0), 1,
-            (ctx.needs_input_grad[0], ctx.needs_input_grad[1], False))
-        return dx, dw
+        need_dx, need_dw = ctx.needs_input_grad[:2]
+        dx = dw = None
+        if (need_dx and ctx.native_bwd
+                and _C.conv3x3s2_bwd_eligible(dy, weight)):
+            dx, need_dx = _C.conv3x3s2_bwd_data(dy, weight), False
+        if need_dx or need_dw:
+            dx_stock, dw, _ = torch.ops.aten.convolution_backward(
+                dy, x, weight, None, (2, 2), (1, 1), (1, 1), False, (0, 0), 1,
+                (need_dx, need_dw, False))
+            dx = dx_stock if need_dx else dx
+        return dx, dw, None, None
 
 
 def _conv3x3_weight(conv, x, stride):
@@ -600,19 +627,28 @@ def _takes(mode, plan):
 
 def _conv3x3_s2(conv, x, bn):
     """``_conv3x3`` for stride 2: through ``_Conv3x3S2`` where the native
-    forward is to run, which needs a training ``bn`` to take its partials."""
-    mode = native_conv3x3_s2_mode() if bn is not None else "0"
-    w = _conv3x3_weight(conv, x, (2, 2)) if mode != "0" else None
+    forward is to run, which needs a training ``bn`` to take its partials, or
+    the native input gradient, which needs grad mode; each by its own switch
+    and its plan's table."""
+    fwd_mode = native_conv3x3_s2_mode() if bn is not None else "0"
+    bwd_mode = (native_conv3x3_s2_bwd_mode() if torch.is_grad_enabled()
+                else "0")
+    if fwd_mode == "0" and bwd_mode == "0":
+        return conv(x), None
+    w = _conv3x3_weight(conv, x, (2, 2))
     if w is None:
         return conv(x), None
     shape = (x.shape[0], x.shape[2], x.shape[3], x.shape[1], w.shape[0])
-    if not (_takes(mode, _C.conv3x3s2_fwd_plan(*shape))
-            and _native(bn, x, None)
-            and w.is_contiguous(memory_format=torch.channels_last)
-            and (w.dtype != torch.bfloat16
-                 or _C.conv3x3s2_fwd_eligible(x, w))):
+    fwd = (_takes(fwd_mode, _C.conv3x3s2_fwd_plan(*shape))
+           and _native(bn, x, None)
+           and w.is_contiguous(memory_format=torch.channels_last)
+           and (w.dtype != torch.bfloat16
+                or _C.conv3x3s2_fwd_eligible(x, w)))
+    bwd = (x.requires_grad and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
+           and _takes(bwd_mode, _C.conv3x3s2_bwd_plan(*shape)))
+    if not (fwd or bwd):
         return conv(x), None
-    return _Conv3x3S2.apply(x, w)
+    return _Conv3x3S2.apply(x, w, fwd, bwd)
 
 
 def _conv3x3(conv, x, bn=None):
@@ -622,7 +658,7 @@ def _conv3x3(conv, x, bn=None):
     take its partials), the native weight gradient or the native input
     gradient is to run, each by its own switch and its plan's table; in every
     other case it is the module call itself and ``part`` is None.  Stride 2
-    has a forward only (``_conv3x3_s2``)."""
+    has a forward and an input gradient of its own (``_conv3x3_s2``)."""
     if getattr(conv, "stride", None) == (2, 2):
         return _conv3x3_s2(conv, x, bn)
     fwd_mode = native_conv3x3_mode() if bn is not None else "0"
