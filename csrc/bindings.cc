@@ -1489,6 +1489,116 @@ at::Tensor py_conv3x3_wrw_ring_fill(int64_t batch, int64_t h, int64_t w,
   return out;
 }
 
+// ---- 3x3 stride-2 convolution backward-weights ------------------------------
+
+Conv3x3S2WrwPlan conv3x3s2_wrw_plan_of(const at::Tensor& dy,
+                                       const at::Tensor& x,
+                                       int64_t max_workgroups = 0) {
+  return conv3x3s2_wrw_plan(x.size(0), x.size(2), x.size(3), x.size(1),
+                            dy.size(1), max_workgroups);
+}
+
+// dy and x as the BatchNorm kernels take them, of one batch, x with even
+// sides twice dy's.
+bool py_conv3x3s2_wrw_eligible(const at::Tensor& dy, const at::Tensor& x) {
+  return bn_tensor_ok(dy) && bn_tensor_ok(x) && x.device() == dy.device() &&
+         x.size(0) == dy.size(0) && x.size(2) == 2 * dy.size(2) &&
+         x.size(3) == 2 * dy.size(3) && conv3x3s2_wrw_plan_of(dy, x).eligible;
+}
+
+// Gradient of conv2d(x, weight, stride=2, padding=1) for the [N, C, 3, 3]
+// weight: (dy, x) -> dw, as py_conv3x3_wrw
+at::Tensor py_conv3x3s2_wrw(const at::Tensor& dy, const at::Tensor& x,
+                            int64_t max_workgroups) {
+  TORCH_CHECK(max_workgroups >= 0, "conv3x3s2_wrw: max_workgroups >= 0");
+  TORCH_CHECK(py_conv3x3s2_wrw_eligible(dy, x),
+              "conv3x3s2_wrw: dy or x is not eligible");
+  const Conv3x3S2WrwPlan p = conv3x3s2_wrw_plan_of(dy, x, max_workgroups);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dy.device().index());
+  auto dw = at::empty({p.n, p.c, 3, 3}, dy.options(),
+                      at::MemoryFormat::ChannelsLast);
+  auto part =
+      at::empty({p.splits, p.n, 9 * p.c}, dy.options().dtype(at::kFloat));
+  launch_conv3x3s2_wrw(p, dy.data_ptr(), x.data_ptr(),
+                       conv3x3_ring_zeros(dy.device().index()),
+                       part.data_ptr<float>(), dw.data_ptr(), bn_stream(dy));
+  return dw;
+}
+
+py::dict py_conv3x3s2_wrw_plan(int64_t batch, int64_t h, int64_t w, int64_t c,
+                               int64_t n, int64_t max_workgroups) {
+  const Conv3x3S2WrwPlan p =
+      conv3x3s2_wrw_plan(batch, h, w, c, n, max_workgroups);
+  py::dict d;
+  d["eligible"] = p.eligible;
+  d["native"] = p.native;
+  d["threads"] = kConvThreads;
+  d["ntiles_n"] = p.ntiles_n;
+  d["ntiles_k"] = p.ntiles_k;
+  d["pitch"] = p.pitch;
+  d["images"] = p.images;
+  d["group_rows"] = p.group_rows;
+  d["hr"] = p.hr;
+  d["chunks_per_image"] = p.chunks_per_image;
+  d["chunks"] = p.chunks;
+  d["live"] = p.live;
+  d["strip_dy"] = p.strip_dy;
+  d["plane_base"] = std::vector<int>(p.plane_base, p.plane_base + 4);
+  d["plane_size"] = std::vector<int>(p.plane_size, p.plane_size + 4);
+  d["stage_pos"] = p.stage_pos;
+  d["glds"] = p.glds;
+  d["max_glds"] = kConv3x3RingMaxGlds;
+  d["stage_bytes"] = p.stage_bytes;
+  d["splits"] = p.splits;
+  d["grid"] = p.grid;
+  d["chunks_per_split"] = p.chunks_per_split;
+  d["lds_bytes"] = p.lds_bytes;
+  d["lds_budget"] = kConvLdsBytes;
+  d["partial_floats"] = p.partial_floats;
+  return d;
+}
+
+// Test seam: the geometry functions of conv3x3s2_wrw replayed on the host.
+// `fill`[wave, j, lane] is (position of the stage, 16-byte vector of the 64
+// channels, 1 for X, pixel of that tensor that `chunk` loads or -1 for
+// zeros) of the 16 bytes that lane `lane` of instruction j of `wave` moves;
+// `taps`[tap] is (plane, first position of the plane in the stage + offset):
+// what is added to a dY position to find the tap's X position.
+py::tuple py_conv3x3s2_wrw_fill(int64_t batch, int64_t h, int64_t w, int64_t c,
+                                int64_t n, int64_t max_workgroups,
+                                int64_t chunk) {
+  const Conv3x3S2WrwPlan p =
+      conv3x3s2_wrw_plan(batch, h, w, c, n, max_workgroups);
+  TORCH_CHECK(p.eligible, "conv3x3s2_wrw_fill: shape is not eligible");
+  TORCH_CHECK(chunk >= 0 && chunk < p.chunks, "conv3x3s2_wrw_fill: chunk");
+  const int waves = kConvThreads / 64;
+  const auto opts = at::TensorOptions().dtype(at::kLong);
+  auto fill = at::empty({waves, p.glds, 64, 4}, opts);
+  int64_t* e = fill.data_ptr<int64_t>();
+  const Conv3x3S2WrwWindow win = conv3x3s2_wrw_window(p, (int)chunk);
+  for (int wave = 0; wave < waves; wave++)
+    for (int j = 0; j < p.glds; j++)
+      for (int lane = 0; lane < 64; lane++, e += 4) {
+        const Conv3x3RingSlot s = conv3x3s2_wrw_slot(wave, j, lane);
+        const Conv3x3S2WrwSrc src = conv3x3s2_wrw_src(p, s.pos);
+        const bool live =
+            (unsigned)(src.key - win.first) < (unsigned)win.count;
+        e[0] = s.pos;
+        e[1] = s.vec;
+        e[2] = src.is_x;
+        e[3] = !live ? -1
+                     : (int64_t)(src.is_x ? win.pixel_x : win.pixel_dy) +
+                           src.pixel;
+      }
+  auto taps = at::empty({9, 2}, opts);
+  for (int tap = 0; tap < 9; tap++) {
+    const Conv3x3S2WrwTap t = conv3x3s2_wrw_tap(p, tap);
+    taps[tap][0] = t.plane;
+    taps[tap][1] = p.plane_base[t.plane] + t.offset;
+  }
+  return py::make_tuple(fill, taps);
+}
+
 // ---- 3x3 convolution forward with statistics --------------------------------
 
 Conv3x3FwdPlan conv3x3_fwd_plan_of(const at::Tensor& x, const at::Tensor& w,
@@ -2493,7 +2603,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Test seam: [waves, instructions, 64, 5] int64, (stage byte, is X, "
         "strip position, vector, pixel or -1) of every 16 bytes of the fill "
         "of one stage with `chunk`.");
-  m.def("conv3x3_stats", &cgx::py_conv3x3_stats, py::arg("x"),
+  m.def("conv3x3s2_wrw", &cgx::py_conv3x3s2_wrw, py::arg("dy"), py::arg("x"),
+        py::arg("max_workgroups") = 0,
+        "Gradient of conv2d(x, weight, stride=2, padding=1) for the 3x3 "
+        "weight, x with even sides: (dy, x) -> dw bf16 [N, C, 3, 3] in "
+        "channels_last, by the native implicit GEMM on four parity planes of "
+        "x; the same bits on every run.  max_workgroups > 0 caps the grid.");
+  m.def("conv3x3s2_wrw_eligible", &cgx::py_conv3x3s2_wrw_eligible,
+        py::arg("dy"), py::arg("x"),
+        "True where conv3x3s2_wrw takes (dy, x): CUDA, bf16, dense "
+        "channels_last, one batch, x's even sides twice dy's, channels powers "
+        "of two in 64..512.");
+  m.def("conv3x3s2_wrw_plan", &cgx::py_conv3x3s2_wrw_plan, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("c"), py::arg("n"),
+        py::arg("max_workgroups") = 0,
+        "The launch geometry of conv3x3s2_wrw for x [batch, c, h, w], and "
+        "`native`: whether the model uses it for this problem.");
+  m.def("conv3x3s2_wrw_fill", &cgx::py_conv3x3s2_wrw_fill, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("c"), py::arg("n"),
+        py::arg("max_workgroups"), py::arg("chunk"),
+        "Test seam: (fill [waves, instructions, 64, 4] int64: (stage "
+        "position, vector, is X, pixel or -1) of every 16 bytes of the fill of "
+        "one stage with `chunk`; taps [9, 2]: (plane, stage position that the "
+        "tap adds to a dY position)).");
+  m.def("conv3x3_stats",&cgx::py_conv3x3_stats, py::arg("x"),
         py::arg("weight"), py::arg("max_workgroups") = 0,
         "conv2d(x, weight, padding=1) of a 3x3 / stride 1 convolution by the "
         "native implicit GEMM -> (y, part): part are the BatchNorm partials "

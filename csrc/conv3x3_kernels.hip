@@ -3,7 +3,8 @@
 // also produces BatchNorm partials (conv3x3_stats, below it) and the input
 // gradient (conv3x3_bwd_data), each with its own description; between
 // the last two the forward of the 3x3 / stride 2 / padding 1 convolution
-// (conv3x3s2_stats) and last its input gradient (conv3x3s2_bwd_data).
+// (conv3x3s2_stats), last its input gradient (conv3x3s2_bwd_data), and after
+// the ring its weight gradient (conv3x3s2_wrw).
 // Geometry: conv3x3_plan.h.
 //
 // dW[n][(3r+s)*C + c] = sum over pixels of dY[b, h, w, n] * X[b, h+r-1, w+s-1, c].
@@ -468,6 +469,208 @@ void launch_wrw3x3_ring(const Conv3x3WrwRingPlan& p, const void* dy,
       hipFuncAttributeMaxDynamicSharedMemorySize, kConvLdsBytes);
   CGX_HIP_CHECK(attr);
   hipLaunchKernelGGL(conv3x3_wrw_ring, dim3(p.grid), dim3(kT), p.lds_bytes,
+                     stream, static_cast<const uint4*>(dy),
+                     static_cast<const uint4*>(x),
+                     static_cast<const uint4*>(zeros), part, p);
+  CGX_HIP_CHECK(hipGetLastError());
+}
+
+// ---- stride-2 weight gradient ---------------------------------------------------
+//
+// dW of the 3x3 / stride 2 / padding 1 convolution (plan: conv3x3s2_wrw_plan,
+// which has the geometry): conv3x3_wrw_ring's tile, ring, waits and steps
+// (ring_steps) on a stage that holds dY's strip and the four parity planes of
+// X as one wrw_cell<64> image.  Tap (r, s) reads plane (r != 1, s != 1) at
+// conv3x3s2_wrw_tap's offset from the position, so the nine B operands again
+// differ by an LDS address only: no masks and no loads per tap.
+//
+// Fill.  The destination of an instruction is the wave's contiguous 1 KiB, so
+// the de-interleaving, like the swizzle, is in the address a lane loads from:
+// conv3x3s2_wrw_slot gives the stage position of its 16 bytes and
+// conv3x3s2_wrw_src what that position holds on every chunk, two pixels apart
+// along a row of a plane.  dY's strip is whole instructions, so which tensor
+// an instruction reads is uniform.  A load whose key the chunk's window does
+// not admit reads `zeros`.  A stage is at most 20 instructions a wave, X four
+// times dY's: the 40 vectors a thread would stage through registers.
+//
+// Bank conflicts.  conv3x3_wrw's argument holds unchanged.  A transposed read
+// takes four consecutive positions of the stage image, starting anywhere, and
+// their columns are 2*(r & 1) + (u ^ ((r >> 1) & 1)): all four differ.  A
+// plane's base is a multiple of four positions, 512 bytes, which moves a
+// read by whole pairs of lines and leaves its columns as they are, and the
+// tap offsets are what r*P + s was: any start.  A step adds 16 positions and
+// an operand's second read 4, as there.
+// conv3x3_wrw_ring's steps of one stage, an even number of them, for
+// conv3x3s2_wrw: the A operand from LDS address pa, tap t's B operand from
+// pb[t].  (conv3x3_wrw_ring keeps its own copy: calling this one changes its
+// register allocation.)
+__device__ __forceinline__ void ring_steps(f32x16 (&acc)[9], unsigned pa,
+                                           unsigned (&pb)[9], int steps_n) {
+  constexpr int kStep = 16 * 2 * 64;  // bytes of a 16-position step
+  constexpr int kHi = 4 * 2 * 64;     // ... and to an operand's second read
+  u32x2 a[2][2], b[2][9][2];
+  // the reads of tap TAP of this step (NEXT 0) or the one after it, into
+  // register set SET
+  auto read = [&](auto set_, auto tap_, auto next_)
+                  __attribute__((always_inline)) {
+    constexpr int SET = decltype(set_)::value, TAP = decltype(tap_)::value;
+    constexpr int O = decltype(next_)::value * kStep;
+    if constexpr (TAP == 0) {
+      a[SET][0] = ring_read_tr<O>(pa);
+      a[SET][1] = ring_read_tr<O + kHi>(pa);
+    }
+    b[SET][TAP][0] = ring_read_tr<O>(pb[TAP]);
+    b[SET][TAP][1] = ring_read_tr<O + kHi>(pb[TAP]);
+  };
+  // one step from register set SET; LAST: no step follows
+  auto step = [&](auto set_, auto last_) __attribute__((always_inline)) {
+    constexpr int SET = decltype(set_)::value;
+    constexpr bool LAST = decltype(last_)::value;
+    ring_for<0, 9>([&](auto tap_) __attribute__((always_inline)) {
+      constexpr int TAP = decltype(tap_)::value, AHEAD = TAP + kRingAhead;
+      if constexpr (AHEAD < 9) {
+        read(set_, std::integral_constant<int, AHEAD>{},
+             std::integral_constant<int, 0>{});
+        ring_wait_lgkmcnt<2 * kRingAhead>();
+      } else if constexpr (!LAST) {
+        read(std::integral_constant<int, SET ^ 1>{},
+             std::integral_constant<int, AHEAD - 9>{},
+             std::integral_constant<int, 1>{});
+        ring_wait_lgkmcnt<2 * kRingAhead + 2>();  // with the A operand
+      } else {
+        ring_wait_lgkmcnt<2 * (8 - TAP)>();
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      acc[TAP] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+          ring_pair(a[SET]), ring_pair(b[SET][TAP]), acc[TAP], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    });
+    pa += kStep;
+#pragma unroll
+    for (int tap = 0; tap < 9; tap++) pb[tap] += kStep;
+  };
+  ring_for<0, kRingAhead>([&](auto tap_) __attribute__((always_inline)) {
+    read(std::integral_constant<int, 0>{}, tap_,
+         std::integral_constant<int, 0>{});
+  });
+  // an even count (the plan's strip_dy): one path, so that no accumulator
+  // is copied where two would meet
+  for (int s = 2; s < steps_n; s += 2) {
+    step(std::integral_constant<int, 0>{}, std::false_type{});
+    step(std::integral_constant<int, 1>{}, std::false_type{});
+  }
+  step(std::integral_constant<int, 0>{}, std::false_type{});
+  step(std::integral_constant<int, 1>{}, std::true_type{});
+}
+
+__global__ __launch_bounds__(kT) void conv3x3s2_wrw(
+    const uint4* __restrict__ dy, const uint4* __restrict__ x,
+    const uint4* __restrict__ zeros, float* __restrict__ part,
+    Conv3x3S2WrwPlan p) {
+  extern __shared__ uint4 lds[];
+  constexpr int C = 64;  // the image
+  constexpr int G = kConv3x3RingMaxGlds;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int c = lane & 31, h = lane >> 5;
+  const int wn = wave >> 1, wk = wave & 1;
+  const int tile = conv3x3_wrw_tile(p, blockIdx.x);
+  const int split = conv3x3_wrw_split(p, blockIdx.x);
+  const int n0 = (tile / p.ntiles_k) * C, k0 = (tile % p.ntiles_k) * C;
+
+  // as conv3x3_wrw_ring, from the start of a stage
+  const int q = (lane >> 2) & 3;
+  const int in_cell = 32 * ((lane >> 4) & 1) + 8 * (lane & 3);
+  const unsigned an = wrw_cell<C>(8 * h + q, wn) + in_cell;
+  unsigned ak[9];
+#pragma unroll
+  for (int tap = 0; tap < 9; tap++) {
+    const Conv3x3S2WrwTap t = conv3x3s2_wrw_tap(p, tap);
+    ak[tap] =
+        wrw_cell<C>(p.plane_base[t.plane] + t.offset + 8 * h + q, wk) + in_cell;
+  }
+
+  f32x16 acc[9];
+#pragma unroll
+  for (int tap = 0; tap < 9; tap++)
+#pragma unroll
+    for (int e = 0; e < 16; e++) acc[tap][e] = 0.f;
+
+  // the lane's 16 bytes of instruction j of a stage: see above
+  const int dy_glds = p.strip_dy / 32;
+  int off[G], key[G];
+#pragma unroll
+  for (int j = 0; j < G; j++) {
+    off[j] = 0, key[j] = kConv3x3RingNever;
+    if (j < p.glds) {  // uniform
+      const Conv3x3RingSlot s = conv3x3s2_wrw_slot(wave, j, lane);
+      const Conv3x3S2WrwSrc src = conv3x3s2_wrw_src(p, s.pos);
+      off[j] = (src.pixel * (src.is_x ? p.c : p.n) + s.vec * 8) * 2;
+      key[j] = src.key;
+    }
+  }
+
+  // the chunks split, split + splits, ... below p.chunks
+  const int T = (p.chunks - split + p.splits - 1) / p.splits;
+  const char* dy_b = reinterpret_cast<const char*>(dy) + n0 * 2;
+  const char* x_b = reinterpret_cast<const char*>(x) + k0 * 2;
+  auto issue = [&](int t, int slot) __attribute__((always_inline)) {
+    const Conv3x3S2WrwWindow win =
+        conv3x3s2_wrw_window(p, split + t * p.splits);
+    const char* src_n = dy_b + (int64_t)win.pixel_dy * p.n * 2;
+    const char* src_k = x_b + (int64_t)win.pixel_x * p.c * 2;
+    lds_char* dst =
+        (lds_char*)reinterpret_cast<char*>(lds) + slot * p.stage_bytes +
+        wave * 1024;
+#pragma unroll
+    for (int j = 0; j < G; j++)
+      if (j < p.glds) {  // uniform
+        const bool live = (unsigned)(key[j] - win.first) < (unsigned)win.count;
+        const char* src = (j < dy_glds ? src_n : src_k) + off[j];
+        __builtin_amdgcn_global_load_lds(
+            (global_cvoid*)(live ? src : reinterpret_cast<const char*>(zeros)),
+            dst + j * 4096, 16, 0, 0);
+      }
+  };
+
+  const int steps_n = p.strip_dy / 16;
+  if (0 < T) issue(0, 0);
+  if (1 < T) issue(1, 1);
+  const unsigned ring_addr =
+      (unsigned)(unsigned long)(lds_char*)reinterpret_cast<char*>(lds);
+  for (int t = 0; t < T; t++) {
+    const unsigned stage = ring_addr + (t & 1) * p.stage_bytes;
+    ring_wait_vmcnt<G>(t + 1 < T ? p.glds : 0);
+    __builtin_amdgcn_s_barrier();
+    unsigned pb[9];
+#pragma unroll
+    for (int tap = 0; tap < 9; tap++) pb[tap] = stage + ak[tap];
+    ring_steps(acc, stage + an, pb, steps_n);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    if (t + 2 < T) issue(t + 2, t & 1);
+  }
+
+  // as conv3x3_wrw
+  const int64_t ld = 9 * (int64_t)p.c;
+  float* out = part + (int64_t)split * p.n * ld;
+#pragma unroll
+  for (int tap = 0; tap < 9; tap++)
+#pragma unroll
+    for (int e = 0; e < 16; e++) {
+      const int n = n0 + wn * 32 + acc_row(e, h);
+      const int k = k0 + wk * 32 + c;
+      out[n * ld + tap * p.c + k] = acc[tap][e];
+    }
+}
+
+void launch_wrw3x3s2(const Conv3x3S2WrwPlan& p, const void* dy, const void* x,
+                     const void* zeros, float* part, hipStream_t stream) {
+  static const hipError_t attr = hipFuncSetAttribute(
+      reinterpret_cast<const void*>(&conv3x3s2_wrw),
+      hipFuncAttributeMaxDynamicSharedMemorySize, kConvLdsBytes);
+  CGX_HIP_CHECK(attr);
+  hipLaunchKernelGGL(conv3x3s2_wrw, dim3(p.grid), dim3(kT), p.lds_bytes,
                      stream, static_cast<const uint4*>(dy),
                      static_cast<const uint4*>(x),
                      static_cast<const uint4*>(zeros), part, p);
@@ -1493,6 +1696,25 @@ void launch_conv3x3_wrw_ring(const Conv3x3WrwRingPlan& p, const void* dy,
                   zeros != nullptr,
               "conv3x3_wrw_ring: plan and kernel disagree");
   launch_wrw3x3_ring(p, dy, x, zeros, part, stream);
+  launch_wrw_finalize(part, dw, p.splits, (int64_t)p.n * 9 * p.c, stream);
+}
+
+void launch_conv3x3s2_wrw(const Conv3x3S2WrwPlan& p, const void* dy,
+                          const void* x, const void* zeros, float* part,
+                          void* dw, hipStream_t stream) {
+  TORCH_CHECK(p.eligible, "conv3x3s2_wrw: shape is not eligible");
+  const int last = p.plane_base[0] + p.plane_size[0];
+  TORCH_CHECK(p.bn == 64 && p.bk == 64 && p.glds <= kConv3x3RingMaxGlds &&
+                  p.strip_dy % 32 == 0 && p.live <= p.strip_dy &&
+                  p.plane_base[3] == p.strip_dy && last <= p.stage_pos &&
+                  p.plane_base[0] + p.strip_dy <= p.stage_pos &&
+                  p.stage_pos == 32 * p.glds &&
+                  p.stage_bytes == p.glds * 4096 &&
+                  p.lds_bytes == 2 * p.stage_bytes &&
+                  p.lds_bytes <= kConvLdsBytes && p.splits <= p.chunks &&
+                  zeros != nullptr,
+              "conv3x3s2_wrw: plan and kernel disagree");
+  launch_wrw3x3s2(p, dy, x, zeros, part, stream);
   launch_wrw_finalize(part, dw, p.splits, (int64_t)p.n * 9 * p.c, stream);
 }
 

@@ -74,6 +74,16 @@ constexpr Measured3x3 kNativeFwd3x3S2[] = {
 // one process.  The table is empty and all three stay stock.
 constexpr std::array<Measured3x3, 0> kNativeBwd3x3S2 = {};
 
+// The same rule for conv3x3s2_wrw plus the finalize against MIOpen's stride-2
+// fill + igemm + cast (benchmarks/conv3x3_s2_wrw_shapes.py); batch, H, W of
+// the input.  All three strided problems of ResNet-50 at batch 256 met it, in
+// two processes.
+constexpr Measured3x3 kNativeWrw3x3S2[] = {
+    {256, 56, 56, 128, 128},
+    {256, 28, 28, 256, 256},
+    {256, 14, 14, 512, 512},
+};
+
 bool pow2_in(int64_t v, int64_t lo, int64_t hi) {
   return v >= lo && v <= hi && (v & (v - 1)) == 0;
 }
@@ -248,6 +258,93 @@ Conv3x3WrwRingPlan conv3x3_wrw_ring_plan(int64_t batch, int64_t h, int64_t w,
   p.partial_floats = (int64_t)p.splits * p.n * 9 * p.c;
   p.magic_pitch = magic_of(p.pitch);
   p.magic_h1 = magic_of(p.h + 1);
+  return p;
+}
+
+namespace {
+
+// The stage of chunks of `rows` output rows; false where it is not within
+// kConv3x3RingMaxGlds instructions a wave.
+bool s2_wrw_stage(Conv3x3S2WrwPlan& p, int rows) {
+  p.live = rows * p.pitch;
+  p.strip_dy = ring_strip_dy_of(rows, p.pitch);
+  int base = p.strip_dy, reach = 0;
+  for (int plane = 3; plane >= 0; plane--) {
+    const int top = (plane >> 1) * p.pitch + (plane & 1);  // the largest offset
+    p.plane_base[plane] = base;
+    p.plane_size[plane] = round_up(p.live + top, 4);
+    reach = std::max(reach, base + top + p.strip_dy);
+    base += p.plane_size[plane];
+  }
+  p.strip_x = base - p.strip_dy;
+  p.stage_pos = round_up(std::max(base, reach), 32);
+  p.glds = p.stage_pos / 32;
+  p.stage_bytes = p.glds * 4096;
+  p.lds_bytes = 2 * p.stage_bytes;
+  return p.glds <= kConv3x3RingMaxGlds && p.lds_bytes <= kConvLdsBytes;
+}
+
+}  // namespace
+
+Conv3x3S2WrwPlan conv3x3s2_wrw_plan(int64_t batch, int64_t h, int64_t w,
+                                    int64_t c, int64_t n,
+                                    int64_t max_workgroups) {
+  Conv3x3S2WrwPlan p;
+  p.bn = p.bk = 64;
+  p.eligible = pow2_in(c, 64, 512) && pow2_in(n, 64, 512) && batch >= 1 &&
+               h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0 &&
+               batch <= kBnMaxRows && h <= kBnMaxRows && w <= kBnMaxRows &&
+               batch * h * w <= kBnMaxRows;
+  if (p.eligible) {
+    p.pitch = (int)w / 2 + 1;
+    p.eligible = s2_wrw_stage(p, 1);
+  }
+  if (!p.eligible) return p;
+  p.batch = (int)batch, p.h = (int)h, p.w = (int)w, p.c = (int)c, p.n = (int)n;
+  p.ho = p.h / 2, p.wo = p.w / 2;
+  for (const Measured3x3& m : kNativeWrw3x3S2)
+    p.native |= m.batch == batch && m.h == h && m.w == w && m.c == c && m.n == n;
+  p.ntiles_n = p.n / p.bn;
+  p.ntiles_k = p.c / p.bk;
+  const int tiles = p.ntiles_n * p.ntiles_k;
+
+  // conv3x3_wrw_plan's splits, the operands being dY's R rows and X's 4R
+  const int64_t rows = batch * p.ho * p.wo;
+  const int64_t operand_bytes =
+      2 * rows * (n * p.ntiles_k + 4 * c * p.ntiles_n);
+  const int64_t by_bytes = std::max<int64_t>(1, operand_bytes / (72 * n * c));
+  int64_t splits = std::min<int64_t>(by_bytes, std::max(1, kConvCus / tiles));
+  if (max_workgroups > 0)
+    splits = std::min(splits, std::max<int64_t>(
+                                  1, std::min<int64_t>(max_workgroups, 1 << 20) /
+                                         tiles));
+  int limit = 1;
+  while (limit + 1 <= (int)std::min<int64_t>(batch * (p.ho + 1), 1 << 10) &&
+         s2_wrw_stage(p, limit + 1))
+    limit++;
+  // set_chunks on the output rows
+  const int whole = std::min((limit + 1) / (p.ho + 1), p.batch);
+  if (whole >= 2) {
+    p.images = whole;
+    p.group_rows = whole * (p.ho + 1) - 1;
+    p.chunks_per_image = 1;
+    p.hr = p.group_rows;
+  } else {
+    p.images = 1;
+    p.group_rows = p.ho;
+    p.chunks_per_image = (p.ho + limit - 1) / limit;
+    p.hr = (p.ho + p.chunks_per_image - 1) / p.chunks_per_image;
+  }
+  p.chunks = (p.batch + p.images - 1) / p.images * p.chunks_per_image;
+  s2_wrw_stage(p, p.hr);
+  splits = std::min<int64_t>(splits, p.chunks);
+  if (splits > 8) splits -= splits % 8;  // conv3x3_wrw_split
+  p.splits = (int)splits;
+  p.grid = tiles * p.splits;
+  p.chunks_per_split = (p.chunks + p.splits - 1) / p.splits;
+  p.partial_floats = (int64_t)p.splits * p.n * 9 * p.c;
+  p.magic_pitch = magic_of(p.pitch);
+  p.magic_h1 = magic_of(p.ho + 1);
   return p;
 }
 

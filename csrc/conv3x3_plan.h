@@ -1,8 +1,9 @@
 // Launch geometry of the weight gradient of a 3x3 / stride 1 / padding 1
 // convolution (conv3x3_wrw in conv3x3_kernels.hip) and, further down, of its
 // forward with BatchNorm partials (conv3x3_stats) and of its input gradient
-// (conv3x3_bwd_data); between them the stride-2 forward (conv3x3s2_stats) and
-// last the stride-2 input gradient (conv3x3s2_bwd_data).
+// (conv3x3_bwd_data); between them the stride-2 forward (conv3x3s2_stats),
+// last the stride-2 input gradient (conv3x3s2_bwd_data), and after the ring
+// the stride-2 weight gradient (conv3x3s2_wrw).
 //
 // Pure host arithmetic, like conv1x1_plan.h.  dW[n, c, r, s] = sum over b, h, w
 // of dY[b, n, h, w] * X[b, c, h+r-1, w+s-1] on channels_last bf16 tensors is
@@ -194,6 +195,129 @@ __host__ __device__ inline Conv3x3RingWindow conv3x3_wrw_ring_window(
 void launch_conv3x3_wrw_ring(const Conv3x3WrwRingPlan& p, const void* dy,
                              const void* x, const void* zeros, float* part,
                              void* dw, hipStream_t stream);
+
+// ---- stride-2 weight gradient (conv3x3s2_wrw) ----------------------------------
+//
+// dW[n][(3r+s)*C + c] = sum over (b, oh, ow) of dY[b, oh, ow, n] *
+// X[b, 2*oh + r - 1, 2*ow + s - 1, c] for the 3x3 / stride 2 / padding 1
+// convolution of an image with even H and W, Ho = H/2, Wo = W/2: the tile, the
+// splits, the walk over chunks and the partials of conv3x3_wrw, loaded as
+// conv3x3_wrw_ring loads them.  A chunk is `hr` output rows of pitch
+// P = Wo + 1 and dY the strip of positions j = row*P + ow, as above.  Four
+// consecutive positions have inputs two pixels apart, so X is de-interleaved
+// into four parity planes, plane 2*pr + pc holding input pixel
+// (2*oh + pr, 2*ow + pc) of output pixel (row, ow) at index
+//
+//   i = (row + pr)*P + ow + pc
+//
+// A pr == 1 plane starts with the output row before the chunk (or a zero row)
+// and a pc == 1 plane has a zero column 0; a pc == 0 plane has its zero
+// column at ow == Wo, under dY's pad.  The pr == 0 planes have no halo row.
+// Tap (r, s) pairs position j with index j + conv3x3s2_wrw_tap(p, 3r+s).offset
+// of plane (r != 1, s != 1); the offset is 0 .. pr*P + pc.  With even sides
+// only r == 0 at oh == 0 and s == 0 at ow == 0 leave the image and reach the
+// zero row or column.  Every input pixel of a chunk's footprint is in exactly
+// one plane slot.
+//
+// A stage is one wrw_cell<64> image of `stage_pos` positions: dY's strip
+// (strip_dy, a multiple of 32, so the dY / X border is a border of
+// instructions and the 16-position steps are even in number), then planes 3,
+// 2, 1, 0, each the indices that a position below hr*P reaches, rounded to 4.
+// The positions from hr*P to strip_dy hold zeros in dY and reach on into the
+// next region of the stage; the stage ends no earlier than the last of them
+// reaches.  Every byte of a stage is written on every chunk, so those zeros
+// meet data of this chunk or zeros, never stale bytes.  Two 7x7 images with
+// the zero row between them are 640 positions, 80 KiB, exactly.
+struct Conv3x3S2WrwPlan : Conv3x3WrwPlan {  // h, w: the input's
+  int ho = 0, wo = 0;
+  int live = 0;  // hr * pitch: the positions past it are zeros on every chunk
+  // plane 2*pr + pc: first position in the stage, and positions
+  int plane_base[4] = {}, plane_size[4] = {};
+  int stage_pos = 0;    // positions of a stage, a multiple of 32
+  int glds = 0;         // instructions of a wave per stage: stage_pos / 32
+  int stage_bytes = 0;  // glds * 4096; lds_bytes = 2 * stage_bytes
+};
+
+// C and N powers of two in [64, 512], H and W even, batch*H*W within
+// kBnMaxRows and Wo narrow enough for one output row to be a stage
+// (Wo <= 87).  `max_workgroups` > 0 caps the grid.  group_rows and hr are
+// output rows; strip_x is the positions of the four planes together.
+Conv3x3S2WrwPlan conv3x3s2_wrw_plan(int64_t batch, int64_t h, int64_t w,
+                                    int64_t c, int64_t n,
+                                    int64_t max_workgroups = 0);
+
+// The plane and the offset from position j of tap = 3r + s.
+struct Conv3x3S2WrwTap {
+  int plane, offset;
+};
+__host__ __device__ inline Conv3x3S2WrwTap conv3x3s2_wrw_tap(
+    const Conv3x3S2WrwPlan& p, int tap) {
+  const int r = tap / 3, s = tap % 3, pr = r != 1, pc = s != 1;
+  return {2 * pr + pc, (r == 2 ? p.pitch : 0) + (s == 2 ? 1 : 0)};
+}
+
+// What position `pos` of a stage loads, whatever the chunk, as
+// conv3x3_wrw_ring_src: the tensor, the pixel relative to the chunk's first
+// (of dY, or of X, conv3x3s2_wrw_window) and the key.  The key is the output
+// row relative to the chunk's first, -1 for the halo row, or with several
+// images the image of the group.
+struct Conv3x3S2WrwSrc {
+  bool is_x;
+  int pixel, key;
+};
+__host__ __device__ inline Conv3x3S2WrwSrc conv3x3s2_wrw_src(
+    const Conv3x3S2WrwPlan& p, int pos) {
+  const bool is_x = pos >= p.strip_dy;
+  int pr = 0, pc = 0, i = pos;
+  if (is_x) {
+    const int plane = (pos < p.plane_base[2]) + (pos < p.plane_base[1]) +
+                      (pos < p.plane_base[0]);  // the planes lie 3, 2, 1, 0
+    i = pos - p.plane_base[plane];
+    if (pos >= p.stage_pos || i >= p.plane_size[plane])
+      return {true, 0, kConv3x3RingNever};
+    pr = plane >> 1, pc = plane & 1;
+  }
+  const int rr = (int)(((unsigned)i * p.magic_pitch) >> kConv3x3MagicShift);
+  const int ow = i - rr * p.pitch - pc, t = rr - pr;
+  if (t >= p.hr || ow < 0 || ow >= p.wo) return {is_x, 0, kConv3x3RingNever};
+  int image = 0, oh = t, key = t;
+  if (p.images > 1) {
+    if (t < 0) return {is_x, 0, kConv3x3RingNever};
+    image = (int)(((unsigned)t * p.magic_h1) >> kConv3x3MagicShift);
+    oh = t - image * (p.ho + 1);
+    if (oh >= p.ho) return {is_x, 0, kConv3x3RingNever};
+    key = image;
+  }
+  if (!is_x) return {false, (image * p.ho + oh) * p.wo + ow, key};
+  return {true, (image * p.h + 2 * oh + pr) * p.w + 2 * ow + pc, key};
+}
+// The chunk's first pixel of dY and of X and the keys it admits.
+struct Conv3x3S2WrwWindow {
+  int pixel_dy, pixel_x, first, count;
+};
+__host__ __device__ inline Conv3x3S2WrwWindow conv3x3s2_wrw_window(
+    const Conv3x3S2WrwPlan& p, int chunk) {
+  const int group = chunk / p.chunks_per_image;
+  if (p.images > 1)
+    return {group * p.images * p.ho * p.wo, group * p.images * p.h * p.w, 0,
+            p.batch - group * p.images};
+  const int t0 = (chunk - group * p.chunks_per_image) * p.hr;
+  return {(group * p.ho + t0) * p.wo, (group * p.h + 2 * t0) * p.w, -t0, p.ho};
+}
+// The position of the stage that the 16 bytes of `lane` of instruction j of
+// `wave` are (conv1x1_wrw_ring_piece), and their 16-byte vector of the 64
+// channels.
+__host__ __device__ inline Conv3x3RingSlot conv3x3s2_wrw_slot(int wave, int j,
+                                                              int lane) {
+  const WrwImageSlot s = conv1x1_wrw_image_slot(
+      64, conv1x1_wrw_ring_piece(wave, j) + 16 * lane);
+  return {false, s.row, s.channel / 8};
+}
+
+// As launch_conv3x3_wrw_ring, dy[B, Ho, Wo, N] and x[B, H, W, C].
+void launch_conv3x3s2_wrw(const Conv3x3S2WrwPlan& p, const void* dy,
+                          const void* x, const void* zeros, float* part,
+                          void* dw, hipStream_t stream);
 
 // ---- forward with BatchNorm partials (conv3x3_stats) -------------------------
 //

@@ -70,8 +70,10 @@ planes in LDS and hands ``bn`` its statistics likewise;
 ``CGX_NATIVE_CONV3X3_S2`` switches it, on its own.  Their input gradient is
 native as well (``_C.conv3x3s2_bwd_data``): the four pixels of every 2x2 cell
 of dX are four sums over the rows of dY, nine products in all and none with an
-inserted zero; ``CGX_NATIVE_CONV3X3_S2_BWD`` switches it, on its own, and
-their weight gradient is the stock one.
+inserted zero; ``CGX_NATIVE_CONV3X3_S2_BWD`` switches it, on its own.  So is their weight
+gradient (``_C.conv3x3s2_wrw``, the ring of ``_C.conv3x3_wrw_ring`` on four
+parity planes of the input, the same bits on every run);
+``CGX_NATIVE_CONV3X3_S2_WRW`` switches it, on its own.
 
 ``conv_stem_bn_act_pool(conv, bn, x, pool)`` is
 ``bn_act_pool(bn, conv(x), pool)`` for the stem, ``Conv2d(3, 64, 7, stride=2,
@@ -561,19 +563,32 @@ def native_conv3x3_s2_bwd_mode() -> str:
     return os.environ.get("CGX_NATIVE_CONV3X3_S2_BWD", "1")
 
 
+def native_conv3x3_s2_wrw_mode() -> str:
+    """``CGX_NATIVE_CONV3X3_S2_WRW``, the switch of the stride-2 weight
+    gradient (``_C.conv3x3s2_wrw``), with the values of
+    ``CGX_NATIVE_CONV3X3_WRW``.  Off where ``CGX_FUSED_BN`` is; no other
+    switch reaches it."""
+    if not fused_bn_enabled():
+        return "0"
+    return os.environ.get("CGX_NATIVE_CONV3X3_S2_WRW", "1")
+
+
 class _Conv3x3S2(torch.autograd.Function):
     """``(y, part) = f(x, weight)``: ``conv2d(x, weight, stride=2,
     padding=1)``, by ``_C.conv3x3s2_stats`` with the BatchNorm partials of
     ``y`` where ``native_fwd`` says so, else stock with ``part`` None.  With
-    ``native_bwd`` the input gradient comes from ``_C.conv3x3s2_bwd_data``
+    ``native_bwd`` the input gradient comes from ``_C.conv3x3s2_bwd_data`` and
+    with ``native_wrw`` the weight gradient from ``_C.conv3x3s2_wrw``, each
     where it takes the gradient that arrives; the stock backward computes
-    what remains, the weight gradient always."""
+    what remains and is not called where nothing does."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
-    def forward(ctx, x, weight, native_fwd=True, native_bwd=False):
+    def forward(ctx, x, weight, native_fwd=True, native_bwd=False,
+                native_wrw=False):
         ctx.save_for_backward(x, weight)
         ctx.native_bwd = native_bwd
+        ctx.native_wrw = native_wrw
         if native_fwd:
             y, part = _C.conv3x3s2_stats(x, weight)
             ctx.mark_non_differentiable(part)
@@ -589,12 +604,15 @@ class _Conv3x3S2(torch.autograd.Function):
         if (need_dx and ctx.native_bwd
                 and _C.conv3x3s2_bwd_eligible(dy, weight)):
             dx, need_dx = _C.conv3x3s2_bwd_data(dy, weight), False
+        if need_dw and ctx.native_wrw and _C.conv3x3s2_wrw_eligible(dy, x):
+            dw, need_dw = _C.conv3x3s2_wrw(dy, x), False
         if need_dx or need_dw:
-            dx_stock, dw, _ = torch.ops.aten.convolution_backward(
+            dx_stock, dw_stock, _ = torch.ops.aten.convolution_backward(
                 dy, x, weight, None, (2, 2), (1, 1), (1, 1), False, (0, 0), 1,
                 (need_dx, need_dw, False))
             dx = dx_stock if need_dx else dx
-        return dx, dw, None, None
+            dw = dw_stock if need_dw else dw
+        return dx, dw, None, None, None
 
 
 def _conv3x3_weight(conv, x, stride):
@@ -627,13 +645,15 @@ def _takes(mode, plan):
 
 def _conv3x3_s2(conv, x, bn):
     """``_conv3x3`` for stride 2: through ``_Conv3x3S2`` where the native
-    forward is to run, which needs a training ``bn`` to take its partials, or
-    the native input gradient, which needs grad mode; each by its own switch
-    and its plan's table."""
+    forward is to run, which needs a training ``bn`` to take its partials,
+    the native input gradient or the native weight gradient, which need grad
+    mode; each by its own switch and its plan's table."""
     fwd_mode = native_conv3x3_s2_mode() if bn is not None else "0"
     bwd_mode = (native_conv3x3_s2_bwd_mode() if torch.is_grad_enabled()
                 else "0")
-    if fwd_mode == "0" and bwd_mode == "0":
+    wrw_mode = (native_conv3x3_s2_wrw_mode() if torch.is_grad_enabled()
+                else "0")
+    if fwd_mode == "0" and bwd_mode == "0" and wrw_mode == "0":
         return conv(x), None
     w = _conv3x3_weight(conv, x, (2, 2))
     if w is None:
@@ -646,9 +666,11 @@ def _conv3x3_s2(conv, x, bn):
                 or _C.conv3x3s2_fwd_eligible(x, w)))
     bwd = (x.requires_grad and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
            and _takes(bwd_mode, _C.conv3x3s2_bwd_plan(*shape)))
-    if not (fwd or bwd):
+    wrw = (w.requires_grad
+           and _takes(wrw_mode, _C.conv3x3s2_wrw_plan(*shape)))
+    if not (fwd or bwd or wrw):
         return conv(x), None
-    return _Conv3x3S2.apply(x, w, fwd, bwd)
+    return _Conv3x3S2.apply(x, w, fwd, bwd, wrw)
 
 
 def _conv3x3(conv, x, bn=None):
