@@ -1254,6 +1254,95 @@ at::Tensor py_conv1x1_tiled_bwd_walk(int64_t rows, int64_t k, int64_t n,
       conv1x1_tiled_bwd_plan(rows, k, n, with_add, max_workgroups));
 }
 
+// ---- 1x1 / stride 2 convolution forward with statistics ----------------------
+
+Conv1x1S2Plan conv1x1s2_plan_of(const at::Tensor& x, const at::Tensor& w,
+                                int64_t max_workgroups = 0) {
+  return conv1x1s2_plan(x.size(0), x.size(2), x.size(3), x.size(1), w.size(0),
+                        max_workgroups);
+}
+
+// the tensors of py_conv1x1_eligible, at a shape conv1x1s2_plan takes
+bool py_conv1x1s2_eligible(const at::Tensor& x, const at::Tensor& weight) {
+  return bn_tensor_ok(x) && conv_weight_ok(weight, x) &&
+         weight.size(1) == x.size(1) && conv1x1s2_plan_of(x, weight).eligible;
+}
+
+// conv2d(x, weight, stride=2) for a 1x1 convolution -> (y, part), as
+// py_conv1x1_stats
+std::tuple<at::Tensor, at::Tensor> py_conv1x1s2_stats(const at::Tensor& x,
+                                                      const at::Tensor& weight,
+                                                      int64_t max_workgroups) {
+  TORCH_CHECK(max_workgroups >= 0, "conv1x1s2_stats: max_workgroups >= 0");
+  TORCH_CHECK(py_conv1x1s2_eligible(x, weight),
+              "conv1x1s2_stats: input or weight is not eligible");
+  const Conv1x1S2Plan p = conv1x1s2_plan_of(x, weight, max_workgroups);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device().index());
+  auto y = at::empty({x.size(0), p.n, p.ho, p.wo}, x.options(),
+                     at::MemoryFormat::ChannelsLast);
+  auto part = at::empty({p.splits, p.pstride}, x.options().dtype(at::kFloat));
+  launch_conv1x1s2_stats(p, x.data_ptr(), weight.data_ptr(), y.data_ptr(),
+                         part.data_ptr<float>(), bn_stream(x));
+  return {y, part};
+}
+
+py::dict py_conv1x1s2_plan(int64_t batch, int64_t h, int64_t w, int64_t k,
+                           int64_t n, int64_t max_workgroups) {
+  const Conv1x1S2Plan p = conv1x1s2_plan(batch, h, w, k, n, max_workgroups);
+  py::dict d = conv1x1_plan_dict(p);
+  d["tile_rows"] = p.tile_rows;
+  d["rows"] = p.rows;
+  d["batch"] = p.batch;
+  d["h"] = p.h;
+  d["w"] = p.w;
+  d["ho"] = p.ho;
+  d["wo"] = p.wo;
+  d["stages"] = p.stages;
+  d["stage_bytes"] = p.stage_bytes;
+  d["run"] = p.run;
+  d["pstride"] = p.pstride;
+  d["partial_floats"] = p.partial_floats;
+  return d;
+}
+
+static_assert(kS2TileRows == kTiledTileRows);  // conv1x1_tiled_walk_of
+at::Tensor py_conv1x1s2_walk(int64_t batch, int64_t h, int64_t w, int64_t k,
+                             int64_t n, int64_t max_workgroups) {
+  return conv1x1_tiled_walk_of(
+      conv1x1s2_plan(batch, h, w, k, n, max_workgroups));
+}
+
+// Test seam: for every 16-byte slot of a stage's A image, in LDS order, the
+// (row of the tile, vector of the chunk, input pixel) that the kernel's loads
+// put there in row tile `tile`, replayed lane by lane with the kernel's own
+// functions; -1 where no load writes.
+at::Tensor py_conv1x1s2_source(int64_t batch, int64_t h, int64_t w, int64_t k,
+                               int64_t n, int64_t tile) {
+  const Conv1x1S2Plan p = conv1x1s2_plan(batch, h, w, k, n);
+  TORCH_CHECK(p.eligible, "conv1x1s2_source: shape is not eligible");
+  TORCH_CHECK(tile >= 0 && tile < p.row_tiles, "conv1x1s2_source: no such tile");
+  auto out = at::full({kS2ImageBytes / 16, 3}, -1,
+                      at::TensorOptions().dtype(at::kLong));
+  int64_t* o = out.data_ptr<int64_t>();
+  for (int wave = 0; wave < kConvThreads / 64; wave++)
+    for (int lane = 0; lane < 64; lane++) {
+      int pixel[kS2Glds];
+      conv1x1s2_lane_pixels(p, (int)tile, wave, lane, pixel);
+      const Conv1x1S2Slot first =
+          conv1x1s2_stage_slot(conv1x1s2_piece(wave, 0) / 16 + lane);
+      for (int j = 0; j < kS2Glds; j++) {
+        const int slot = conv1x1s2_piece(wave, j) / 16 + lane;
+        TORCH_CHECK(slot < kS2ImageBytes / 16 && o[3 * slot] == -1,
+                    "conv1x1s2_source: a slot is written twice");
+        // what the kernel loads: row first.row + 32 * j, vector first.vec
+        o[3 * slot] = first.row + 32 * j;
+        o[3 * slot + 1] = first.vec;
+        o[3 * slot + 2] = pixel[j];
+      }
+    }
+  return out;
+}
+
 // ---- 1x1 convolution backward-weights --------------------------------------
 
 // dy and x as the BatchNorm kernels take them, of one batch and image size.
@@ -2518,6 +2607,34 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("with_add") = false, py::arg("max_workgroups") = 0,
         "Test seam: conv1x1_walk for the plan of conv1x1_tiled_bwd_plan; "
         "channels are dx's.");
+  m.def("conv1x1s2_stats", &cgx::py_conv1x1s2_stats, py::arg("x"),
+        py::arg("weight"), py::arg("max_workgroups") = 0,
+        "conv2d(x, weight, stride=2) for a 1x1 / padding 0 convolution on a "
+        "channels_last bf16 activation -> (y, part): 256 x 256 tiles, both "
+        "operands through a ring of LDS stages filled by loads direct to LDS, "
+        "the stride-2 gather in the loads' addresses; part are the BatchNorm "
+        "partials of y in the layout of conv1x1_stats.  The same bits on "
+        "every run.");
+  m.def("conv1x1s2_eligible", &cgx::py_conv1x1s2_eligible, py::arg("x"),
+        py::arg("weight"),
+        "True where conv1x1s2_stats takes (x, weight): the tensors of "
+        "conv1x1_eligible at a shape conv1x1s2_plan admits.");
+  m.def("conv1x1s2_plan", &cgx::py_conv1x1s2_plan, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("k"), py::arg("n"),
+        py::arg("max_workgroups") = 0,
+        "The launch geometry of conv1x1s2_stats for an input [batch, k, h, w] "
+        "and n output channels, and `native`: whether the model uses it "
+        "there.");
+  m.def("conv1x1s2_walk", &cgx::py_conv1x1s2_walk, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("k"), py::arg("n"),
+        py::arg("max_workgroups") = 0,
+        "Test seam: conv1x1_walk for the plan of conv1x1s2_plan.");
+  m.def("conv1x1s2_source", &cgx::py_conv1x1s2_source, py::arg("batch"),
+        py::arg("h"), py::arg("w"), py::arg("k"), py::arg("n"),
+        py::arg("tile") = 0,
+        "Test seam: [2048, 3], for every 16-byte slot of a stage's A image "
+        "the (row of the tile, vector, input pixel) loaded there in row tile "
+        "`tile`.");
   m.def("conv1x1_wrw", &cgx::py_conv1x1_wrw, py::arg("dy"), py::arg("x"),
         py::arg("max_workgroups") = 0,
         "Weight gradient of conv2d(x, weight) for a 1x1 / stride 1 convolution "

@@ -2,6 +2,7 @@
 #include "conv1x1_plan.h"
 
 #include <algorithm>
+#include <array>
 
 namespace cgx {
 namespace {
@@ -263,6 +264,72 @@ Conv1x1WrwRingPlan conv1x1_wrw_ring_plan(int64_t rows, int64_t k, int64_t n,
   p.grid = tiles * p.splits;
   p.chunks_per_split = (p.row_chunks + p.splits - 1) / p.splits;
   p.partial_floats = (int64_t)p.splits * p.n * p.k;
+  return p;
+}
+
+// The strided problems (batch, H, K, N; W = H) at which conv1x1s2_stats plus
+// the join's apply pass met the same rule against MIOpen's forward plus the
+// join with a statistics pass for the downsample BatchNorm, measured with
+// benchmarks/conv1x1_s2_fwd_shapes.py (benchmarks/RESULTS.md): all three
+// downsample convolutions of ResNet-50 at batch 256.  Measured at these
+// problems only.
+struct MeasuredS2 {
+  int batch, h, k, n;
+};
+constexpr std::array<MeasuredS2, 3> kNativeFwd1x1S2 = {{
+    {256, 56, 256, 512}, {256, 28, 512, 1024}, {256, 14, 1024, 2048},
+}};
+
+Conv1x1S2Plan conv1x1s2_plan(int64_t batch, int64_t h, int64_t w, int64_t k,
+                             int64_t n, int64_t max_workgroups) {
+  Conv1x1S2Plan p;
+  if (batch < 1 || h < 1 || w < 1 || batch > kBnMaxRows || h > kBnMaxRows ||
+      w > kBnMaxRows)
+    return p;
+  const int64_t ho = (h + 1) / 2, wo = (w + 1) / 2;
+  if (ho * wo > kBnMaxRows) return p;
+  const int64_t rows = batch * ho * wo;
+  p.rows = rows;
+  p.eligible = pow2_in(k, kS2Kc, 2048) && pow2_in(n, kS2TileChannels, 2048) &&
+               rows >= 2 && rows <= kBnMaxRows &&
+               batch * h * w * (k / 8) <= INT32_MAX;
+  if (!p.eligible) return p;
+  p.k = (int)k;
+  p.n = (int)n;
+  p.batch = (int)batch, p.h = (int)h, p.w = (int)w;
+  p.ho = (int)ho, p.wo = (int)wo;
+  for (const MeasuredS2& m : kNativeFwd1x1S2)
+    p.native |= m.batch == batch && m.h == h && m.h == w && m.k == k &&
+                m.n == n;
+  p.tile_rows = kS2TileRows;
+  p.nt = kS2TileChannels / 32;
+  p.bn = kS2TileChannels;
+  p.ntiles = p.n / p.bn;
+  p.kc = kS2Kc;
+  p.nchunks = p.k / p.kc;
+  p.stages = kS2Stages;
+  p.stage_bytes = kS2StageBytes;
+  p.lds_bytes = p.stages * p.stage_bytes + kConvStageBytes;
+  p.row_tiles = (int)((rows + kS2TileRows - 1) / kS2TileRows);
+  p.b32 = (int)(32 / (ho * wo));
+  p.oh32 = (int)(32 % (ho * wo) / wo);
+  p.ow32 = (int)(32 % wo);
+  p.last_pixel = conv1x1s2_pixel(p, conv1x1s2_pos(p, (int)rows - 1));
+  // One workgroup per CU: LDS and the 256 accumulator registers of a wave
+  // leave no room for a second.  The partials within 5% of the output's
+  // bytes, and the splits a multiple of 8 where that costs no tile, as in
+  // conv1x1_tiled_plan.
+  int64_t splits = std::min<int64_t>(
+      {(int64_t)p.row_tiles, std::max(1, kConvCus / p.ntiles),
+       std::max<int64_t>(1, rows / 82)});
+  const int64_t by8 = splits - splits % 8;
+  if (splits > 8 &&
+      (p.row_tiles + by8 - 1) / by8 == (p.row_tiles + splits - 1) / splits)
+    splits = by8;
+  set_grid(p, splits, max_workgroups);
+  p.run = 64 * p.tiles_per_split;
+  p.pstride = 2 * p.n + p.ntiles;
+  p.partial_floats = (int64_t)p.splits * p.pstride;
   return p;
 }
 

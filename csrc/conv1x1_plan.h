@@ -241,6 +241,109 @@ __host__ __device__ inline int conv1x1_wrw_ring_lds_base(
          conv1x1_wrw_ring_piece(wave, j);
 }
 
+// The forward of the 1x1 / stride 2 / padding 0 convolution, with the
+// BatchNorm partials of its output (conv1x1s2_stats in
+// conv1x1s2_kernels.hip): Y[R, N] = gather(X)[R, K] * W[N, K]^T, R =
+// batch * ho * wo output pixels, row (b, oh, ow) of the gathered matrix the
+// K channels of input pixel (b, 2*oh, 2*ow).  Odd sides are admitted: the
+// last input row or column is then read, and never a pixel outside the image.
+//
+// A workgroup owns a tile of kS2TileRows rows x kS2TileChannels channels, its
+// four waves 2 x 2 with sixteen 32x32 accumulators each.  K goes in chunks of
+// kS2Kc through a ring of `stages` LDS stages; a stage holds the A image
+// [256 rows][64] and behind it the B image [256 channels][64], both in the
+// swizzled layout of the stride-1 kernels (conv1x1s2_stage_slot), filled by
+// global_load_lds_dwordx4.  The walk is that of conv1x1_tiled_plan
+// (conv1x1_tiled_ntile / _split, conv1x1_tile) and the ring runs on across
+// its tiles.  `run`, the per-lane run of the moments, is 64 rows per tile
+// visited; a channel has four runs per workgroup.  The partials have the
+// layout of conv1x1_plan.  `native` is this kernel's own measurement against
+// the stock convolution and the statistics pass it saves.
+constexpr int kS2TileRows = 256;
+constexpr int kS2TileChannels = 256;
+constexpr int kS2Kc = 64;
+constexpr int kS2Stages = 2;
+constexpr int kS2ImageBytes = kS2TileRows * kS2Kc * 2;  // of one operand
+constexpr int kS2StageBytes = 2 * kS2ImageBytes;
+constexpr int kS2Glds = kS2ImageBytes / 4096;  // per wave, stage and operand
+
+struct Conv1x1S2Plan : Conv1x1Plan {
+  int batch = 0, h = 0, w = 0, ho = 0, wo = 0;
+  int tile_rows = 0, stages = 0, stage_bytes = 0;
+  // 32 rows on, as (images, output rows, output columns) with ow32 < wo and
+  // oh32 < ho; the input pixel of row R - 1
+  int b32 = 0, oh32 = 0, ow32 = 0, last_pixel = 0;
+};
+
+// K a power of two in [64, 2048], N one in [256, 2048], H and W at least 1,
+// 2 <= R <= kBnMaxRows and batch * H * W * K / 8 below 2^31: the kernel
+// indexes the 16-byte vectors of X with an int.
+Conv1x1S2Plan conv1x1s2_plan(int64_t batch, int64_t h, int64_t w, int64_t k,
+                             int64_t n, int64_t max_workgroups = 0);
+
+// Output row -> (image, output row, output column) -> input pixel
+// (b * H + 2 * oh) * W + 2 * ow.
+struct Conv1x1S2Pos {
+  int b, oh, ow;
+};
+__host__ __device__ inline Conv1x1S2Pos conv1x1s2_pos(const Conv1x1S2Plan& p,
+                                                      int row) {
+  const int b = row / (p.ho * p.wo), rem = row - b * (p.ho * p.wo);
+  return {b, rem / p.wo, rem % p.wo};
+}
+__host__ __device__ inline int conv1x1s2_pixel(const Conv1x1S2Plan& p,
+                                               Conv1x1S2Pos at) {
+  return (at.b * p.h + 2 * at.oh) * p.w + 2 * at.ow;
+}
+// ... of the row 32 further on, without a division
+__host__ __device__ inline Conv1x1S2Pos conv1x1s2_next32(
+    const Conv1x1S2Plan& p, Conv1x1S2Pos at) {
+  at.ow += p.ow32;
+  if (at.ow >= p.wo) at.ow -= p.wo, at.oh++;
+  at.oh += p.oh32;
+  if (at.oh >= p.ho) at.oh -= p.ho, at.b++;
+  at.b += p.b32;
+  return at;
+}
+
+// The (row, 16-byte vector) of a [256][64] bf16 image that sits at its
+// 16-byte slot `slot`: the inverse of w_slot<64> in the kernels.
+struct Conv1x1S2Slot {
+  int row, vec;
+};
+__host__ __device__ inline Conv1x1S2Slot conv1x1s2_stage_slot(int slot) {
+  const int row = slot >> 3;
+  return {row, (slot & 7) ^ ((row >> 1) & 7)};
+}
+// One global_load_lds_dwordx4 of a wave writes 1 KiB, lane l the slot 16 * l
+// on from a base the wave shares: the j-th of kS2Glds for one image lands
+// this many bytes from the image's start, the four waves on consecutive KiB.
+__host__ __device__ inline int conv1x1s2_piece(int wave, int j) {
+  return (4 * j + wave) * 1024;
+}
+// The row of the tile that `lane` of `wave` fills with its j-th instruction
+// is conv1x1s2_stage_slot(conv1x1s2_piece(wave, j) / 16 + lane).row, 32 * j
+// on from that of j = 0.  Its input pixels in row tile `tile`: rows past R
+// read row R - 1 (they are neither stored nor counted).
+__host__ __device__ inline void conv1x1s2_lane_pixels(
+    const Conv1x1S2Plan& p, int tile, int wave, int lane,
+    int (&pixel)[kS2Glds]) {
+  int row = tile * kS2TileRows +
+            conv1x1s2_stage_slot(conv1x1s2_piece(wave, 0) / 16 + lane).row;
+  Conv1x1S2Pos at = conv1x1s2_pos(p, row < p.rows ? row : 0);
+#pragma unroll
+  for (int j = 0; j < kS2Glds; j++, row += 32) {
+    pixel[j] = row < p.rows ? conv1x1s2_pixel(p, at) : p.last_pixel;
+    at = conv1x1s2_next32(p, at);
+  }
+}
+
+// y[R, N] bf16 and part[splits, pstride] fp32 from x[batch, h, w, K] and
+// w[N, K] bf16; every pointer 16-byte aligned.
+void launch_conv1x1s2_stats(const Conv1x1S2Plan& p, const void* x,
+                            const void* w, void* y, float* part,
+                            hipStream_t stream);
+
 // dw[N, K] bf16 from dy[R, N] and x[R, K] bf16 through part[splits, N, K]
 // fp32, which needs no initialisation; every pointer 16-byte aligned.
 void launch_conv1x1_wrw(const Conv1x1WrwPlan& p, const void* dy, const void* x,

@@ -18,6 +18,7 @@ SOURCES = [
     "csrc/quant_kernels.hip",
     "csrc/bn_kernels.hip",
     "csrc/conv1x1_kernels.hip",
+    "csrc/conv1x1s2_kernels.hip",
     "csrc/conv3x3_kernels.hip",
     "csrc/conv_stem_kernels.hip",
     "csrc/compress.cc",

@@ -53,6 +53,14 @@ switches and the tiled one are off wherever the forward one is, the tiled
 input gradient also wherever ``CGX_NATIVE_CONV1X1_BWD`` is, and the ring
 wherever ``CGX_NATIVE_CONV1X1_WRW`` is.
 
+The three 1x1 / stride 2 downsample convolutions (``identity_conv`` of the
+first block of ``layer2..4``) have a native forward of their own,
+``_C.conv1x1s2_stats`` (csrc/conv1x1s2_kernels.hip): both operands through a
+ring of LDS stages, the stride-2 gather in the loads' addresses, and the
+partials of its output for ``identity_bn``, so that the join needs no
+statistics pass.  ``CGX_NATIVE_CONV1X1_S2`` switches it like the others and
+depends on none of them; both gradients are the stock ones.
+
 ``conv3x3(conv, x)`` is ``conv(x)`` for the 3x3 / stride 1 / padding 1
 convolution of a bottleneck.  Its weight gradient has a native implicit GEMM
 (``_C.conv3x3_wrw``, csrc/conv3x3_kernels.hip) with the fixed summation order
@@ -374,13 +382,60 @@ def _conv1x1_takes(kernel: str, shape, *with_add) -> bool:
     return plan["eligible"] and (plan["native"] or mode == "all")
 
 
-def _conv1x1_shape(conv, bn, x):
-    """(rows, K, N) where everything but the plan admits the native kernels,
+def native_conv1x1_s2_mode() -> str:
+    """``CGX_NATIVE_CONV1X1_S2``, the switch of the stride-2 forward with
+    statistics (``_C.conv1x1s2_stats``): "0" off, "all" every eligible
+    problem, else ("1", the default) the problems its plan has measured
+    faster.  Off where ``CGX_FUSED_BN`` is; no other switch reaches it."""
+    if not fused_bn_enabled():
+        return "0"
+    return os.environ.get("CGX_NATIVE_CONV1X1_S2", "1")
+
+
+class _Conv1x1S2(torch.autograd.Function):
+    """``(y, part) = f(x, weight)``: ``conv2d(x, weight, stride=2)`` for a
+    1x1 convolution by ``_C.conv1x1s2_stats``, with the BatchNorm partials of
+    ``y``.  Both gradients are the stock ones."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
+    def forward(ctx, x, weight):
+        ctx.save_for_backward(x, weight)
+        y, part = _C.conv1x1s2_stats(x, weight)
+        ctx.mark_non_differentiable(part)
+        return y, part
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dy, _dpart):
+        x, weight = ctx.saved_tensors
+        dx, dw, _ = torch.ops.aten.convolution_backward(
+            dy, x, weight, None, (2, 2), (0, 0), (1, 1), False, (0, 0), 1,
+            (ctx.needs_input_grad[0], ctx.needs_input_grad[1], False))
+        return dx, dw
+
+
+def _conv1x1_s2(conv, bn, x):
+    """``_conv`` for the 1x1 / stride 2 convolution of a downsample path:
+    through ``_Conv1x1S2`` where its switch and its plan's table say so."""
+    if _conv1x1_shape(conv, bn, x, (2, 2)) is None:
+        return conv(x), None, x
+    plan = _C.conv1x1s2_plan(x.shape[0], x.shape[2], x.shape[3], x.shape[1],
+                             conv.weight.shape[0])
+    if not _takes(native_conv1x1_s2_mode(), plan):
+        return conv(x), None, x
+    return (*_Conv1x1S2.apply(x, conv.weight), x)
+
+
+def _conv1x1_shape(conv, bn, x, stride=(1, 1)):
+    """(rows, K, N) of the input where everything but the plan admits the
+    native kernels of a 1x1 convolution of that stride, (1, 1) or (2, 2),
     else None."""
-    if native_conv1x1_mode() == "0":
+    s2 = stride == (2, 2)
+    if (native_conv1x1_s2_mode() if s2 else native_conv1x1_mode()) == "0":
         return None
     if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == (1, 1)
-            and conv.stride == (1, 1) and conv.padding == (0, 0)
+            and conv.stride == stride and conv.padding == (0, 0)
             and conv.dilation == (1, 1) and conv.groups == 1
             and conv.bias is None and conv.padding_mode == "zeros"):
         return None
@@ -399,7 +454,8 @@ def _conv1x1_shape(conv, bn, x):
             and (w.dtype == torch.bfloat16
                  or (autocast and w.dtype == torch.float32))):
         return None
-    if w.dtype == torch.bfloat16 and not _C.conv1x1_eligible(x, w):
+    eligible = _C.conv1x1s2_eligible if s2 else _C.conv1x1_eligible
+    if w.dtype == torch.bfloat16 and not eligible(x, w):
         return None  # e.g. a weight view that is not dense or not aligned
     return x.numel() // x.shape[1], x.shape[1], w.shape[0]
 
@@ -408,7 +464,10 @@ def _conv(conv, bn, x, fork=False):
     """``(conv(x), part, skip)``: ``part`` are the partials for ``bn``, or
     None where the stock convolution ran; ``skip`` is what a residual path
     continues from instead of ``x``.  It is ``x`` itself unless ``fork`` is
-    set and the native backward-data is to add the path's gradient."""
+    set and the native backward-data is to add the path's gradient.  Stride
+    2 has a forward of its own (``_conv1x1_s2``)."""
+    if getattr(conv, "stride", None) == (2, 2):
+        return _conv1x1_s2(conv, bn, x)
     shape = _conv1x1_shape(conv, bn, x)
     if shape is None:
         return conv(x), None, x
